@@ -30,7 +30,7 @@ def _run(n, extra, timeout=600, spawn=False):
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
                "--master-addr", "127.0.0.1", f"--master-port={_port()}", BENCH]
-    cmd += ["--gpus", str(n), "--device", "cpu", "--steps", "2", "--warmup", "1"] + extra
+    cmd += ["--gpus", str(n), "--device", "cpu", "--steps", "2", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd="/tmp")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -46,7 +46,7 @@ def _run(n, extra, timeout=600, spawn=False):
     assert out["per_rank"]["ms_per_step_max"] == out["ms_per_step"]
     assert out["launcher"] == ("spawn" if spawn and n > 1 else ("single" if n == 1 else "torchrun"))
     assert "INVALID" in out["config"]["model"]  # a CPU run can never pass for a measurement
-    # box telemetry fields are always present; on CPU they are empty / null
+    # box telemetry fields come with --full; on CPU they are empty / null
     tel = out["telemetry"]
     assert tel["rank0"]["source"] is None and tel["rank0"]["samples"] == 0
     assert len(tel["sclk_mhz_avg_per_rank"]) == n and all(v is None for v in tel["sclk_mhz_avg_per_rank"])
@@ -132,6 +132,45 @@ def test_bench_world8_self_diagnosing_fields(parallel):
     oc = out["comm"]["order_check"]
     assert oc["enabled"] and oc["calls_checked_rank0"] > 0 and oc["steps"] == 1
     assert "rccl_topology" not in out       # gloo: nothing to capture
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without ``--full`` the line keeps the headline fields and drops what only ``--full``
+    measures; ``--dump-outputs`` writes the last timed step's loss, gradient norm and the seeded
+    parameter / gradient samples as float32, identical between two runs of the same arguments."""
+    import numpy as np
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--device", "cpu", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True, text=True,
+                           timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        for k in ("telemetry", "versions", "tunableop", "data_check", "rccl_topology", "profile_ms"):
+            assert k not in out, k
+        files = {p.name: np.load(p) for p in (tmp_path / d).iterdir()}
+        assert set(files) == {"loss.npy", "grad_norm.npy", "params_sample.npy", "grads_sample.npy"}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in files.values())
+        assert files["loss.npy"].shape == (1,) and round(float(files["loss.npy"][0]), 4) == out["final_loss"]
+        assert files["params_sample.npy"].shape == files["grads_sample.npy"].shape
+        assert sum(v.nbytes for v in files.values()) <= 64 * 2 ** 20
+        assert np.abs(files["grads_sample.npy"]).max() > 0
+        dumps.append(files)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
+def test_bench_profile_needs_full():
+    r = subprocess.run([sys.executable, BENCH, "--device", "cpu", "--profile"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--full" in r.stderr
 
 
 def test_bench_random_ids_arm():

@@ -48,7 +48,7 @@ def test_engines_world2_gloo_on_one_gpu():
 BENCH = os.path.join(os.path.dirname(HERE), "bench.py")
 # the headline path at 2 layers: Llama-3-8B dims, FSDP, bf16, --actv_ckpt auto, meta-built init
 SMALL = ["--preset", "llama3_8b_fsdp", "--layers", "2", "--seq_len", "256", "--steps", "3", "--warmup", "1",
-         "--actv_ckpt", "auto", "--data", "fixed_ids"]
+         "--actv_ckpt", "auto", "--data", "fixed_ids", "--full"]
 
 
 def _bench(extra, timeout=420):
