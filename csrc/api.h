@@ -7,6 +7,13 @@
 
 namespace bllm {
 
+// kernel debug mode (common.h BLLM_DEBUG_WORD / BLLM_DASSERT): first failed check code of each
+// translation unit that has checks, reset on read
+unsigned int debug_take_embedding();
+unsigned int debug_take_loss();
+unsigned int debug_take_attn_decode();
+unsigned int debug_take_elementwise();
+
 // norms.hip
 int norm_bwd_num_wg(int N, int d);
 int norm_max_dim(DType dt);
@@ -51,7 +58,19 @@ void dropout_add(DType dt, const void* x, const void* a, void* out, long n, floa
 void rope(DType dt, void* qkv, const float* cosT, const float* sinT, long N, int T, int H, int G, int hd,
           bool inverse, int pos_offset, hipStream_t s, const int* pos_dev = nullptr);
 
-// attention (attn.hip dispatch; attn_mfma.hip / attn_bwd_mfma.hip / attn_f32.hip / attn_naive.hip)
+// bias gradient (column sums): part must hold colsum_bands(N, F) * F floats
+int colsum_bands(int N, int F);
+// op 0: out = dropout_bwd(src), op 1: out = src * gelu'(aux); db (+)= out.sum(0) from the same pass
+// (part == nullptr: no sums); op 1 with act: also act = gelu(aux) (may alias src)
+void bwd_bias_grad(DType dt, DType odt, int op, const void* src, const void* aux, void* out, float* part, void* db,
+                   int N, int F, bool accumulate, float p, uint64_t seed, uint64_t offset, void* act, hipStream_t s);
+void bias_grad(DType dt, DType odt, const void* dy, float* part, void* out, int N, int F, bool accumulate,
+               hipStream_t s);
+// out[e] (+)= sum_s part[s][e] (n % 8 == 0)
+void sum_partials_into(DType pdt, DType odt, const void* part, void* out, long n, int S, bool accumulate,
+                       hipStream_t s);
+
+// attn.hip: dispatch over the kernels below by dtype and head dim
 // keep_mask (dropout > 0, bf16/fp16 MFMA kernels only, else nullptr): the forward writes the
 // attention-dropout keep bits, uint32 words [B*H][ceil(T/32)][T] (bit j of word (kw, q) = key
 // 32kw + j), the backward kernels read them instead of re-hashing every (q, key).  Words of
@@ -61,18 +80,21 @@ bool attn_keep_mask_ok(DType dt, int hd);
 void attn_fwd(DType dt, const void* qkv, void* o, float* lse, int B, int T, int H, int G, int hd, bool causal,
               float p, uint64_t seed, uint64_t offset, uint32_t* keep_mask, hipStream_t s);
 void attn_bwd(DType dt, const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv, float* delta,
-              float* dq_acc, float* dkv_part, int B, int T, int H, int G, int hd, bool causal, float p, uint64_t seed,
-              uint64_t offset, const uint32_t* keep_mask, const float* rcos, const float* rsin, hipStream_t s);
-// GEMM tile -> workgroup placement (map 0 = XCD-contiguous M-bands, 1 = plain order, 2 = N-bands)
-// and group depth (<= 0: default) of the dW kernel and of the forward-layout kernel
-void set_wgrad_tile_map(int map, int group_m);
-void set_gemm_nt_tile_map(int map, int group_m);
+              float* dkv_part, int B, int T, int H, int G, int hd, bool causal, float p, uint64_t seed, uint64_t offset,
+              const uint32_t* keep_mask, const float* rcos, const float* rsin, hipStream_t s);
+
+// attn_mfma.hip: bf16 / fp16 flash-attention forward on the matrix cores (head dims 64 / 128)
 bool attn_mfma_head_dim(int hd);
-void attn_fwd_naive(DType dt, const void* qkv, void* o, float* lse, int B, int T, int H, int G, int hd, bool causal,
-                    float p, uint64_t seed, uint64_t offset, hipStream_t s);
-void attn_bwd_naive(DType dt, const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv,
-                    float* delta, int B, int T, int H, int G, int hd, bool causal, float p, uint64_t seed,
-                    uint64_t offset, hipStream_t s);
+void attn_fwd_mfma(DType dt, const void* qkv, void* o, float* lse, int B, int T, int H, int G, int hd, bool causal,
+                   float p, uint64_t seed, uint64_t offset, uint32_t* keep_mask, hipStream_t s);
+
+// attn_bwd_mfma.hip: its backward (inverse RoPE of dQ / dK fused into the epilogues when rcos is set)
+// whether the dK/dV pass needs the fp32 per-head partial buffer (GQA without the fused-head variant)
+bool attn_bwd_kv_partials(int B, int T, int H, int G);
+void attn_bwd_mfma(DType dt, const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv,
+                   float* delta, float* dkv_part, int B, int T, int H, int G, int hd, bool causal, float p,
+                   uint64_t seed, uint64_t offset, const uint32_t* keep_mask, const float* rcos, const float* rsin,
+                   hipStream_t s);
 
 // attn_f32.hip: fp32 flash attention on v_mfma_f32_32x32x2_f32 (head dims 64 / 128)
 bool attn_f32_head_dim(int hd);
@@ -82,24 +104,14 @@ void attn_bwd_f32(const float* qkv, const float* o, const float* lse, const floa
                   int B, int T, int H, int G, int hd, bool causal, float p, uint64_t seed, uint64_t offset,
                   hipStream_t s);
 
-// whether the dK/dV pass needs the fp32 per-head partial buffer (GQA without the fused-head variant)
-bool attn_bwd_kv_partials(int B, int T, int H, int G);
-
+// attn_naive.hip: scalar kernels for every other head dim and dtype
+void attn_fwd_naive(DType dt, const void* qkv, void* o, float* lse, int B, int T, int H, int G, int hd, bool causal,
+                    float p, uint64_t seed, uint64_t offset, hipStream_t s);
+void attn_bwd_naive(DType dt, const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv,
+                    float* delta, int B, int T, int H, int G, int hd, bool causal, float p, uint64_t seed,
+                    uint64_t offset, hipStream_t s);
 void attn_delta(DType dt, const void* o, const void* dout, float* delta, int B, int T, int H, int hd,
                 hipStream_t s);
-
-// elementwise.hip — bias gradient (column sums), part must hold colsum_bands(N, F) * F floats
-int colsum_bands(int N, int F);
-// op 0: out = dropout_bwd(src), op 1: out = src * gelu'(aux); db (+)= out.sum(0) from the same pass
-// (part == nullptr: no sums); op 1 with act: also act = gelu(aux) (may alias src)
-void bwd_bias_grad(DType dt, DType odt, int op, const void* src, const void* aux, void* out, float* part, void* db,
-                   int N, int F, bool accumulate, float p, uint64_t seed, uint64_t offset, void* act, hipStream_t s);
-void bias_grad(DType dt, DType odt, const void* dy, float* part, void* out, int N, int F, bool accumulate,
-               hipStream_t s);
-
-// elementwise.hip — out[e] (+)= sum_s part[s][e] (n % 8 == 0)
-void sum_partials_into(DType pdt, DType odt, const void* part, void* out, long n, int S, bool accumulate,
-                       hipStream_t s);
 
 // attn_decode.hip — single-query attention over a [B, G, Tmax, hd] KV cache
 int attn_decode_max_len();
@@ -118,11 +130,6 @@ void ce_bwd(DType dt, void* logits, const int64_t* tgt, const float* lse, const 
             long ignore_index, hipStream_t s);
 
 // embedding.hip
-// kernel debug mode (common.h BLLM_DASSERT): first failed check code of each TU, reset on read
-unsigned int debug_take_embedding();
-unsigned int debug_take_loss();
-unsigned int debug_take_attn_decode();
-unsigned int debug_take_elementwise();
 void embedding_fwd(DType dt, const int64_t* idx, const void* wte, const void* wpe, void* out, long N, int d, int T,
                    float p, uint64_t seed, uint64_t offset, long vocab, hipStream_t s);
 long embedding_bwd_part_floats(long N, int d);  // fp32 scratch the token backward needs
@@ -191,6 +198,10 @@ void lora_head_bwd(DType dt, const void* dl, long ldl, const void* st, long ldst
 void lora_pack_t(DType dt, const LoraPackArgs& a, int K, int max_r, hipStream_t s);
 
 // gemm_wgrad.hip — C[M, N] (+)= A^T B with A [K, M], B [K, N] row-major (dW = dY^T X).
+// GEMM tile -> workgroup placement (map 0 = XCD-contiguous M-bands, 1 = plain order, 2 = N-bands)
+// and group depth (<= 0: default) of the dW kernel; set_gemm_nt_tile_map below is the same for
+// the forward-layout kernel
+void set_wgrad_tile_map(int map, int group_m);
 // S > 1: split s writes fp32 partial C + s * c_split (accumulate must be false).
 bool wgrad_gemm_supported(int M, int N, int K, int S);
 bool wgrad_tail_supported(int M, int N, int K, int full, int St);
@@ -206,6 +217,7 @@ void gemm_nn(DType dt, DType odt, const void* a, long lda, const void* b, long l
 
 // gemm_nt.hip — persistent 4-wave forward-layout kernel with 64-deep K-tiles (full 128-B rows):
 // C[M, N] (+)= A[M, K] B[N, K]^T; M, N multiples of 256, K of 128
+void set_gemm_nt_tile_map(int map, int group_m);
 bool gemm_nt2_supported(int M, int N, int K, long lda, long ldb);
 void gemm_nt2(DType dt, DType odt, const void* a, long lda, const void* b, long ldb, void* c, long ldc, int M, int N,
               int K, bool accumulate, hipStream_t s);

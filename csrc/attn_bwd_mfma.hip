@@ -19,93 +19,21 @@
 // delta = rowsum(dO * O) is computed by the dQ kernel (which holds dO in registers anyway
 // and runs first) and handed to the dK/dV kernel through a [B,H,T] fp32 buffer.  Q/dO (dK/dV
 // kernel) and K/V (dQ kernel) tiles arrive by global_load_lds DMA, double-buffered, stored as
-// 16-B-chunk XOR images for MFMA row reads and 64-B-chunk XOR images for hardware-transposed
-// reads (ds_read_b64_tr_b16).  Causal: only tiles at/below the diagonal; heaviest first.
+// row images for MFMA row reads and transposed images for hardware-transposed reads
+// (ds_read_b64_tr_b16), or one dual image for both (layouts: attn_tiles.h).  Causal: only tiles
+// at/below the diagonal; heaviest first.
 #include <float.h>
 #include <stdlib.h>
 #include <type_traits>
 
 #include "api.h"
+#include "attn_tiles.h"
+#include "mma.h"
 
 namespace bllm {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-namespace {
-template <typename T> struct MFb;
-template <> struct MFb<bf16_t> {
-  typedef bf16x8 v8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct MFb<f16_t> {
-  typedef f16x8 v8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
-// 16-B-chunk XOR image (row reads); rows of HD elements
-template <int HD> __device__ __forceinline__ int r_off(int r, int c16) {
-  if constexpr (HD == 128) return r * 256 + ((c16 ^ (r & 15)) << 4);
-  else return r * 128 + ((c16 ^ ((r >> 1) & 7)) << 4);
-}
-// 64-B-chunk XOR image (transposed reads); byte offset of element col in row r
-template <int HD> __device__ __forceinline__ int t_off(int r, int col) {
-  const int c64 = col >> 5, w = (col & 31) << 1;
-  if constexpr (HD == 128) return r * 256 + ((c64 ^ (r & 3)) << 6) + w;
-  else return r * 128 + ((c64 ^ ((r >> 1) & 1)) << 6) + w;
-}
-// ONE image of a [rows][HD] tile serving both 16-B row reads (ds_read_b128, S / dP operands)
-// and hardware-transposed reads (ds_read_b64_tr_b16, dV^T / dK^T operands): chunk ch of row r at
-// ch ^ f(r).  HD 128 (256-B rows): f = ((r&3)<<2) | ((r>>2)&3)  (cdna_hip_programming.md T10 (b)).
-// HD 64 (128-B rows): f = (((r>>1)&1)<<2) | ((r>>2)&3) -- over the 8 same-parity rows of every
-// b128 lane group f is a permutation of 0..7 (row reads conflict-free), and rows r, r+2 of an
-// aligned 4-row block differ in bit 2 (the 4-chunk block a transposed half-wave read touches),
-// so a 32-lane transposed read hits 32 distinct bank pairs.  Depends on r & 15 only.
-template <int HD> __device__ __forceinline__ int dual_f(int r) {
-  if constexpr (HD == 128) return ((r & 3) << 2) | ((r >> 2) & 3);
-  else return (((r >> 1) & 1) << 2) | ((r >> 2) & 3);
-}
-template <int HD> __device__ __forceinline__ int dual_off(int r, int ch) {
-  return r * (HD * 2) + ((ch ^ dual_f<HD>(r)) << 4);
-}
-
-// dS image [32 q][128 keys] bf16: 16-B chunk XOR by q
-__device__ __forceinline__ int ds_off(int q, int key) {
-  return q * 256 + ((((key >> 3) ^ (q & 15))) << 4) + ((key & 7) << 1);
-}
-
-// two floats -> packed pair (one v_cvt_pk_bf16_f32 for bf16)
-template <typename T> __device__ __forceinline__ uint32_t pk2(float a, float b) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  const t2 v = __builtin_convertvector((f2{a, b}), t2);
-  uint32_t u;
-  __builtin_memcpy(&u, &v, 4);
-  return u;
-}
-
-template <typename v8> __device__ __forceinline__ v8 tr8(const char* base, int off_lo, int off_hi) {
-  const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off_lo));
-  const s16x4 r2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + off_hi));
-  // whole-register concatenation (an element-wise short[8] build made hipcc emit a v_bfi per
-  // fragment and wait for the read right there)
-  return __builtin_bit_cast(v8, __builtin_shufflevector(r1, r2, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-}  // namespace
-
 constexpr int BWD_BKV = 128;  // keys per workgroup
 constexpr int BWD_BQ = 32;    // queries per step
-constexpr float kLog2eB = 1.4426950408889634f;
 
 // LDS bytes of one ring slot of the dK/dV kernel: Q rows, Q^T image, dO rows, dO^T image,
 // and a per-wave copy of the step's lse/delta (so each wave's stats DMA is its own)
@@ -113,42 +41,12 @@ template <int HD, bool DUAL = false, bool MASK = false> constexpr int dkdv_buf_b
   return (DUAL ? 2 : 4) * BWD_BQ * HD * 2 + 4 * 256 + (MASK ? 4 * 256 : 0);
 }
 
-// Instruction budget per 32-query step (per wave): 32 MFMAs, 16 b128 + 32 tr_b64 LDS reads at
-// loop-invariant per-lane offsets (+ a per-slot base), ~60 VALU of softmax math (the 1/sqrt(d)
-// of dS is folded into the final dK), 9 saddr LDS-DMA issues whose per-lane offsets are
-// precomputed.  Masking (causal diagonal, sequence tail) and dropout are compile-time variants
-// so the common interior step carries no per-element branches.
-// FUSEG: one workgroup sweeps all H/G query heads of its kv head (dK/dV summed in registers,
-// written once in bf16: no fp32 per-head partials, no reduction kernel); otherwise one query
-// head per workgroup plus the attn_bwd_kv_reduce_k pass for GQA.
-// DUAL: Q and dO each staged as ONE dual-use image (dual_off) instead of a row image plus a
-// transposed image: half the LDS and DMA per step, which buys a 4-slot ring (three steps in
-// flight) at two workgroups per CU -- the 2-slot version waits on its DMA ~60 % of wave cycles.
-// MASK (with DROP): the dropout keep bits come from the forward's keep mask -- one more 4-byte
-// DMA per wave and step brings the 32 words (queries of the step, this wave's 32 keys) into the
-// slot -- instead of one counter hash per (query, key) element.
-// VLDS: the V fragments (B operands of dP = dO V^T) live in LDS -- [32 keys][HD] per wave,
-// 16-B chunks XOR-swizzled by row (r_off) -- instead of 32 VGPRs for the whole kernel: at hd 128
-// K + V fragments (64) + dK/dV accumulators (128) + S/dP (32) leave too little of the 256 VGPRs
-// two waves per SIMD allow, and hipcc spilled the fragments to scratch, reloading them every
-// step behind an s_waitcnt vmcnt(0) that also drained the Q/dO DMA ring.
 // Inverse RoPE in a backward epilogue (rotate_half form, reference common_components.py:6-35):
 // the lane holds elements d..d+3 (d = dc + 8 gq + 4 hh) of the first half in lo and the same
 // elements of the second half (d + HD/2) in hi, so each rotation pair is lane-local:
 //   g1' = g1 c + g2 s,  g2' = g2 c - g1 s   (c, s = cos/sin [T, HD/2] fp32 at position pos).
 // Replaces a separate rope pass over dQ / dK (read + write of [N, (H + G) hd]).  ``row`` is the
 // head's first element.
-// One row-per-lane-pair 16-B store (cdna_hip_programming.md T21): this lane holds the packed
-// columns of groups gq (a) and gq+1 (b), 4 each, 4 hh + 0..3 within the group; one
-// v_permlane32_swap per dword leaves group gq's 8 columns in the lower lane half and gq+1's in the
-// upper, stored at dst = row + 8 gq + 8 hh.  Lanes l and l+32 must hold the same row.
-template <typename T>
-__device__ __forceinline__ void store16_pair(T* dst, const uint32_t (&a)[2], const uint32_t (&b)[2]) {
-  const auto rx = __builtin_amdgcn_permlane32_swap(a[0], b[0], false, false);
-  const auto ry = __builtin_amdgcn_permlane32_swap(a[1], b[1], false, false);
-  *reinterpret_cast<uint4*>(dst) = uint4{rx[0], ry[0], rx[1], ry[1]};
-}
-
 template <typename T, int HD>
 __device__ __forceinline__ void rope_bwd_store(const f32x16& lo, const f32x16& hi, float scale, int hh, int pos,
                                                int dc, const float* __restrict__ rcos,
@@ -169,10 +67,10 @@ __device__ __forceinline__ void rope_bwd_store(const f32x16& lo, const f32x16& h
       o1[j] = g1 * cc[j] + g2 * ss[j];
       o2[j] = g2 * cc[j] - g1 * ss[j];
     }
-    w1[gq][0] = pk2<T>(o1[0], o1[1]);
-    w1[gq][1] = pk2<T>(o1[2], o1[3]);
-    w2[gq][0] = pk2<T>(o2[0], o2[1]);
-    w2[gq][1] = pk2<T>(o2[2], o2[3]);
+    w1[gq][0] = pack2<T>(o1[0], o1[1]);
+    w1[gq][1] = pack2<T>(o1[2], o1[3]);
+    w2[gq][0] = pack2<T>(o2[0], o2[1]);
+    w2[gq][1] = pack2<T>(o2[2], o2[3]);
   }
   // 16-B stores (T21, as attn_fwd_mfma_k's epilogue): lanes l and l+32 hold the same row
 #pragma unroll
@@ -182,6 +80,25 @@ __device__ __forceinline__ void rope_bwd_store(const f32x16& lo, const f32x16& h
   }
 }
 
+// Instruction budget per 32-query step (per wave): 32 MFMAs, 16 b128 + 32 tr_b64 LDS reads at
+// loop-invariant per-lane offsets (+ a per-slot base), ~60 VALU of softmax math (the 1/sqrt(d)
+// of dS is folded into the final dK), 9 saddr LDS-DMA issues whose per-lane offsets are
+// precomputed.  Masking (causal diagonal, sequence tail) and dropout are compile-time variants
+// so the common interior step carries no per-element branches.
+// FUSEG: one workgroup sweeps all H/G query heads of its kv head (dK/dV summed in registers,
+// written once in bf16: no fp32 per-head partials, no reduction kernel); otherwise one query
+// head per workgroup plus the attn_bwd_kv_reduce_k pass for GQA.
+// DUAL: Q and dO each staged as ONE dual-use image (dual_img_off) instead of a row image plus a
+// transposed image: half the LDS and DMA per step, which buys a 4-slot ring (three steps in
+// flight) at two workgroups per CU -- the 2-slot version waits on its DMA ~60 % of wave cycles.
+// MASK (with DROP): the dropout keep bits come from the forward's keep mask -- one more 4-byte
+// DMA per wave and step brings the 32 words (queries of the step, this wave's 32 keys) into the
+// slot -- instead of one counter hash per (query, key) element.
+// VLDS: the V fragments (B operands of dP = dO V^T) live in LDS -- [32 keys][HD] per wave,
+// 16-B chunks XOR-swizzled by row (row_img_off) -- instead of 32 VGPRs for the whole kernel: at hd 128
+// K + V fragments (64) + dK/dV accumulators (128) + S/dP (32) leave too little of the 256 VGPRs
+// two waves per SIMD allow, and hipcc spilled the fragments to scratch, reloading them every
+// step behind an s_waitcnt vmcnt(0) that also drained the Q/dO DMA ring.
 template <typename T, int HD, bool DROP, int NBUF, int OCC, bool FUSEG = false, bool DUAL = false, bool MASK = false,
           bool VLDS = false>
 __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict__ qkv, const T* __restrict__ dout,
@@ -193,7 +110,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
                                                             const uint32_t* __restrict__ kmask,
                                                             const float* __restrict__ rcos,
                                                             const float* __restrict__ rsin, int xmap) {
-  typedef typename MFb<T>::v8 v8;
+  typedef typename Mma<T>::v8 v8;
   constexpr int KK = HD / 16, DT = HD / 32, CH = HD / 8, ROWB = HD * 2;
   constexpr int IMG = BWD_BQ * ROWB;            // bytes of one [32][HD] image
   constexpr int PPW = IMG / 1024 / 4;           // 1-KiB DMA pieces per wave per image
@@ -223,7 +140,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
   const int k0 = kb * BWD_BKV;
   const int kw0 = k0 + 32 * w;
   const int mykey = kw0 + l32;
-  const float scale = rsqrtf((float)HD), c = scale * kLog2eB;
+  const float scale = rsqrtf((float)HD), c = scale * kLog2e;
 
   // ---- K / V fragments of this wave's 32 keys (B operands, key = lane column)
   constexpr int VOFF = NBUF * BUF;              // VLDS: per-wave V rows after the ring
@@ -235,7 +152,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
       kf[kk] = *reinterpret_cast<const v8*>(kb_ + (long)kr * rs + kk * 16 + hh * 8);
       const v8 vv = *reinterpret_cast<const v8*>(vb_ + (long)kr * rs + kk * 16 + hh * 8);
       if constexpr (VLDS)
-        *reinterpret_cast<v8*>(smem + VOFF + w * 32 * ROWB + r_off<HD>(l32, kk * 2 + hh)) = vv;
+        *reinterpret_cast<v8*>(smem + VOFF + w * 32 * ROWB + row_img_off<HD>(l32, kk * 2 + hh)) = vv;
       else
         vf[kk] = vv;
     }
@@ -260,11 +177,9 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
     const int P = w * 64 + lane;
     const int r = P / CH, pc = P % CH;
     int rc;
-    if constexpr (DUAL) rc = pc ^ dual_f<HD>(r);
-    else if constexpr (HD == 128) rc = pc ^ (r & 15);
-    else rc = pc ^ ((r >> 1) & 7);
-    const int c64 = (pc >> 2) ^ (HD == 128 ? (r & 3) : ((r >> 1) & 1));
-    const int tc = c64 * 4 + (pc & 3);
+    if constexpr (DUAL) rc = dual_img_src16<HD>(r, pc);
+    else rc = BLLM_ROW_IMG_SRC16(HD, r, pc);
+    const int tc = BLLM_TR_IMG_SRC16(HD, r, pc);
     q_r = (uint32_t)(r * rs * 2 + rc * 16);
     q_t = (uint32_t)(r * rs * 2 + tc * 16);
     o_r = (uint32_t)(r * ors * 2 + rc * 16);
@@ -311,11 +226,9 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
         const int P = (w + 4 * j) * 64 + lane;
         const int r = P / CH, pc = P % CH;
         int rc;
-        if constexpr (DUAL) rc = pc ^ dual_f<HD>(r);
-        else if constexpr (HD == 128) rc = pc ^ (r & 15);
-        else rc = pc ^ ((r >> 1) & 7);
-        const int c64 = (pc >> 2) ^ (HD == 128 ? (r & 3) : ((r >> 1) & 1));
-        const int tc = c64 * 4 + (pc & 3);
+        if constexpr (DUAL) rc = dual_img_src16<HD>(r, pc);
+        else rc = BLLM_ROW_IMG_SRC16(HD, r, pc);
+        const int tc = BLLM_TR_IMG_SRC16(HD, r, pc);
         const uint32_t pd = (w + 4 * j) * 1024;
         const int rr = min(q0 + r, T_ - 1);
         glds16(qb_ + (long)rr * rs + rc * 8, lb + pd);
@@ -383,12 +296,12 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
       f32x16 sacc = f32x16{}, dpacc = f32x16{};
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
-        const int ro = DUAL ? dual_off<HD>(l32_, kk * 2 + hh_) : r_off<HD>(l32_, kk * 2 + hh_);
-        sacc = MFb<T>::mma(*reinterpret_cast<const v8*>(S + ro), kf[kk], sacc);
+        const int ro = DUAL ? dual_img_off<HD>(l32_, kk * 2 + hh_) : row_img_off<HD>(l32_, kk * 2 + hh_);
+        sacc = Mma<T>::mma(*reinterpret_cast<const v8*>(S + ro), kf[kk], sacc);
         v8 vk;
-        if constexpr (VLDS) vk = *reinterpret_cast<const v8*>(smem + VOFF + w * 32 * ROWB + r_off<HD>(l32_, kk * 2 + hh_));
+        if constexpr (VLDS) vk = *reinterpret_cast<const v8*>(smem + VOFF + w * 32 * ROWB + row_img_off<HD>(l32_, kk * 2 + hh_));
         else vk = vf[kk];
-        dpacc = MFb<T>::mma(*reinterpret_cast<const v8*>(S + IOR + ro), vk, dpacc);
+        dpacc = Mma<T>::mma(*reinterpret_cast<const v8*>(S + IOR + ro), vk, dpacc);
       }
       // rows of this lane's accumulator registers: q = q0 + 4hh + off, off = (r&3) + 8(r>>2);
       // visible iff lo <= off <= hi (causal: q >= key; q < T; key < T)
@@ -441,8 +354,8 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
           uint32_t u[4], v[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            u[j] = pk2<T>(sacc[8 * s2 + 2 * j], sacc[8 * s2 + 2 * j + 1]);
-            v[j] = pk2<T>(dpacc[8 * s2 + 2 * j], dpacc[8 * s2 + 2 * j + 1]);
+            u[j] = pack2<T>(sacc[8 * s2 + 2 * j], sacc[8 * s2 + 2 * j + 1]);
+            v[j] = pack2<T>(dpacc[8 * s2 + 2 * j], dpacc[8 * s2 + 2 * j + 1]);
           }
           __builtin_memcpy(&pf, u, 16);
           __builtin_memcpy(&df, v, 16);
@@ -453,16 +366,16 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
           if constexpr (DUAL) {
             // lane 4q+p of a 16-lane group: row 4hh+q (+8), columns dt*32 + glb*16 + 4p .. +3
             const int row = 4 * hh_ + qrow + s2 * 16, ch = dt * 4 + glb * 2 + (pcol >> 1);
-            olo = dual_off<HD>(row, ch) + 8 * (pcol & 1);
-            ohi = dual_off<HD>(row + 8, ch) + 8 * (pcol & 1);
+            olo = dual_img_off<HD>(row, ch) + 8 * (pcol & 1);
+            ohi = dual_img_off<HD>(row + 8, ch) + 8 * (pcol & 1);
           } else {
-            olo = t_off<HD>(4 * hh_ + qrow, dt * 32 + glb * 16 + pcol * 4) + s2 * 16 * ROWB;
+            olo = tr_img_off<HD>(4 * hh_ + qrow, dt * 32 + glb * 16 + pcol * 4) + s2 * 16 * ROWB;
             ohi = olo + 8 * ROWB;
           }
-          const v8 ao = tr8<v8>(S + IOT, olo, ohi);
-          dv[dt] = MFb<T>::mma(ao, pf, dv[dt]);
-          const v8 aq = tr8<v8>(S + IQT, olo, ohi);
-          dk[dt] = MFb<T>::mma(aq, df, dk[dt]);
+          const v8 ao = tr_read8<v8>(S + IOT, olo, ohi);
+          dv[dt] = Mma<T>::mma(ao, pf, dv[dt]);
+          const v8 aq = tr_read8<v8>(S + IQT, olo, ohi);
+          dk[dt] = Mma<T>::mma(aq, df, dk[dt]);
         }
       }
     }
@@ -485,10 +398,10 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
       for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int gq = 0; gq < 4; gq += 2) {
-          const uint32_t a[2] = {pk2<T>(dk[dt][4 * gq] * scale, dk[dt][4 * gq + 1] * scale),
-                                 pk2<T>(dk[dt][4 * gq + 2] * scale, dk[dt][4 * gq + 3] * scale)};
-          const uint32_t c[2] = {pk2<T>(dk[dt][4 * gq + 4] * scale, dk[dt][4 * gq + 5] * scale),
-                                 pk2<T>(dk[dt][4 * gq + 6] * scale, dk[dt][4 * gq + 7] * scale)};
+          const uint32_t a[2] = {pack2<T>(dk[dt][4 * gq] * scale, dk[dt][4 * gq + 1] * scale),
+                                 pack2<T>(dk[dt][4 * gq + 2] * scale, dk[dt][4 * gq + 3] * scale)};
+          const uint32_t c[2] = {pack2<T>(dk[dt][4 * gq + 4] * scale, dk[dt][4 * gq + 5] * scale),
+                                 pack2<T>(dk[dt][4 * gq + 6] * scale, dk[dt][4 * gq + 7] * scale)};
           store16_pair<T>(pk + dt * 32 + 8 * gq + 8 * hh, a, c);
         }
     }
@@ -496,8 +409,8 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_mfma_k(const T* __restrict_
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int gq = 0; gq < 4; gq += 2) {
-        const uint32_t a[2] = {pk2<T>(dv[dt][4 * gq], dv[dt][4 * gq + 1]), pk2<T>(dv[dt][4 * gq + 2], dv[dt][4 * gq + 3])};
-        const uint32_t c[2] = {pk2<T>(dv[dt][4 * gq + 4], dv[dt][4 * gq + 5]), pk2<T>(dv[dt][4 * gq + 6], dv[dt][4 * gq + 7])};
+        const uint32_t a[2] = {pack2<T>(dv[dt][4 * gq], dv[dt][4 * gq + 1]), pack2<T>(dv[dt][4 * gq + 2], dv[dt][4 * gq + 3])};
+        const uint32_t c[2] = {pack2<T>(dv[dt][4 * gq + 4], dv[dt][4 * gq + 5]), pack2<T>(dv[dt][4 * gq + 6], dv[dt][4 * gq + 7])};
         store16_pair<T>(pv + dt * 32 + 8 * gq + 8 * hh, a, c);
       }
   } else if (mykey < T_) {
@@ -538,7 +451,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_k(const T* __restrict__ 
                                                         const uint32_t* __restrict__ kmask,
                                                         const float* __restrict__ rcos,
                                                         const float* __restrict__ rsin, int xmap) {
-  typedef typename MFb<T>::v8 v8;
+  typedef typename Mma<T>::v8 v8;
   constexpr int KK = HD / 16, DT = HD / 32, CH = HD / 8, ROWB = HD * 2;
   constexpr int IMG = DQ_BK * ROWB;             // bytes of one [BK][HD] image
   constexpr int LD = DQ_BK * CH / 256;          // 1-KiB pieces per wave per image
@@ -571,7 +484,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_k(const T* __restrict__ 
   const int wq_lo = q0 + w * 32, wq_hi = wq_lo + 31;
   const int qi = wq_lo + l32;
   const int qc = qi < T_ ? qi : T_ - 1;
-  const float scale = rsqrtf((float)HD), c = scale * kLog2eB;
+  const float scale = rsqrtf((float)HD), c = scale * kLog2e;
   DropSlab ds;
   uint64_t dslab = 0;
   if constexpr (DROP) {
@@ -612,20 +525,17 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_k(const T* __restrict__ 
 
   int roff[KK];
 #pragma unroll
-  for (int kk = 0; kk < KK; ++kk) roff[kk] = r_off<HD>(l32, kk * 2 + hh);
+  for (int kk = 0; kk < KK; ++kk) roff[kk] = row_img_off<HD>(l32, kk * 2 + hh);
   int troff[DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) troff[dt] = t_off<HD>(4 * hh + qrow, dt * 32 + gl * 16 + pcol * 4);
+  for (int dt = 0; dt < DT; ++dt) troff[dt] = tr_img_off<HD>(4 * hh + qrow, dt * 32 + gl * 16 + pcol * 4);
   uint32_t roffg[LD], toffg[LD];
   int prow[LD], prc[LD], ptc[LD];
 #pragma unroll
   for (int i = 0; i < LD; ++i) {
     const int P = (w * LD + i) * 64 + lane;
     const int r = P / CH, pc = P % CH;
-    int rc;
-    if constexpr (HD == 128) rc = pc ^ (r & 15); else rc = pc ^ ((r >> 1) & 7);
-    const int c64 = (pc >> 2) ^ (HD == 128 ? (r & 3) : ((r >> 1) & 1));
-    const int tc = c64 * 4 + (pc & 3);
+    const int rc = BLLM_ROW_IMG_SRC16(HD, r, pc), tc = BLLM_TR_IMG_SRC16(HD, r, pc);
     prow[i] = r; prc[i] = rc; ptc[i] = tc;
     roffg[i] = (uint32_t)(r * rs * 2 + rc * 16);
     toffg[i] = (uint32_t)(r * rs * 2 + tc * 16);
@@ -699,8 +609,8 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_k(const T* __restrict__ 
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
         const int off = kt * 32 * ROWB + roff[kk];
-        sc[kt] = MFb<T>::mma(*reinterpret_cast<const v8*>(KR + off), qf[kk], sc[kt]);
-        dp[kt] = MFb<T>::mma(*reinterpret_cast<const v8*>(VR + off), of[kk], dp[kt]);
+        sc[kt] = Mma<T>::mma(*reinterpret_cast<const v8*>(KR + off), qf[kk], sc[kt]);
+        dp[kt] = Mma<T>::mma(*reinterpret_cast<const v8*>(VR + off), of[kk], dp[kt]);
       }
     }
     // keys of this lane's accumulator rows: k0 + 32kt + (r&3) + 8(r>>2) + 4hh
@@ -759,14 +669,14 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_k(const T* __restrict__ 
         {
           uint32_t u[4];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) u[j] = pk2<T>(sc[kt][8 * s2 + 2 * j], sc[kt][8 * s2 + 2 * j + 1]);
+          for (int j = 0; j < 4; ++j) u[j] = pack2<T>(sc[kt][8 * s2 + 2 * j], sc[kt][8 * s2 + 2 * j + 1]);
           __builtin_memcpy(&df, u, 16);
         }
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const int o = troff[dt] + (kt * 32 + s2 * 16) * ROWB;
-          const v8 a = tr8<v8>(KT, o, o + 8 * ROWB);
-          dq[dt] = MFb<T>::mma(a, df, dq[dt]);
+          const v8 a = tr_read8<v8>(KT, o, o + 8 * ROWB);
+          dq[dt] = Mma<T>::mma(a, df, dq[dt]);
         }
       }
     ring_wait(t);
@@ -789,10 +699,10 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_k(const T* __restrict__ 
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int gq = 0; gq < 4; gq += 2) {
-        const uint32_t a[2] = {pk2<T>(dq[dt][4 * gq] * scale, dq[dt][4 * gq + 1] * scale),
-                               pk2<T>(dq[dt][4 * gq + 2] * scale, dq[dt][4 * gq + 3] * scale)};
-        const uint32_t c[2] = {pk2<T>(dq[dt][4 * gq + 4] * scale, dq[dt][4 * gq + 5] * scale),
-                               pk2<T>(dq[dt][4 * gq + 6] * scale, dq[dt][4 * gq + 7] * scale)};
+        const uint32_t a[2] = {pack2<T>(dq[dt][4 * gq] * scale, dq[dt][4 * gq + 1] * scale),
+                               pack2<T>(dq[dt][4 * gq + 2] * scale, dq[dt][4 * gq + 3] * scale)};
+        const uint32_t c[2] = {pack2<T>(dq[dt][4 * gq + 4] * scale, dq[dt][4 * gq + 5] * scale),
+                               pack2<T>(dq[dt][4 * gq + 6] * scale, dq[dt][4 * gq + 7] * scale)};
         store16_pair<T>(row + dt * 32 + 8 * gq + 8 * hh, a, c);
       }
   }
@@ -920,10 +830,9 @@ static void launch_bwd(const BwdArgs& a, bool drop, bool fuseg, dim3 grid_q, dim
 }
 
 void attn_bwd_mfma(DType dt, const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv,
-                   float* delta, float* dq_acc, float* dkv_part, int B, int T_, int H, int G, int hd, bool causal,
-                   float p, uint64_t seed, uint64_t offset, const uint32_t* keep_mask, const float* rcos,
-                   const float* rsin, hipStream_t s) {
-  (void)dq_acc;
+                   float* delta, float* dkv_part, int B, int T_, int H, int G, int hd, bool causal, float p,
+                   uint64_t seed, uint64_t offset, const uint32_t* keep_mask, const float* rcos, const float* rsin,
+                   hipStream_t s) {
   const int nkb = (T_ + BWD_BKV - 1) / BWD_BKV;
   const bool fuseg = fuse_gqa_heads(B, T_, H, G);
   dim3 grid_kv(nkb * (fuseg ? G : H) * B), grid_q(((T_ + DQ_BQ - 1) / DQ_BQ) * H * B);

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_k(const T* __restrict
       else st16(vb + (long)p * HD + c * 8, ld16(vnew + c * 8));
     }
   }
-  const float c = scale * 1.4426950408889634f;
+  const float c = scale * kLog2e;
 
   float qf[HD];
 #pragma unroll

@@ -22,14 +22,11 @@
 // over the query heads of its kv group and 32-query tiles; no atomics, deterministic).
 #include <float.h>
 #include "api.h"
+#include "mma.h"
 
 namespace bllm {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int BQ = 128;  // rows (queries, or keys in dK/dV) per workgroup: 4 waves x 32
 constexpr int BT = 32;   // streamed tile (keys, or queries in dK/dV)
 

@@ -20,64 +20,23 @@
 // K/V tiles of 64 keys, register DMA (global_load_lds) of tile t+1 under the MFMAs of tile t,
 // double-buffered LDS.  GQA reads kv head h / (H/G)
 // directly; causal tiles above the diagonal are skipped; q-blocks are launched
-// heaviest-first.  LDS images are XOR-swizzled: K in 16-B chunks (conflict-free
-// ds_read_b128 row reads), V in 64-B chunks (conflict-free transposed reads).
+// heaviest-first.  LDS images are XOR-swizzled (attn_tiles.h): K is a row image (conflict-free
+// ds_read_b128 row reads), V a transposed image (conflict-free transposed reads).
 // Attention-probability dropout (GPT-2) uses the stateless counter hash of common.h.
 #include <float.h>
 #include <stdlib.h>
 
 #include <type_traits>
 #include "api.h"
+#include "attn_tiles.h"
+#include "mma.h"
 
 namespace bllm {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-template <typename T> struct MF;
-template <> struct MF<bf16_t> {
-  typedef bf16x8 v8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct MF<f16_t> {
-  typedef f16x8 v8;
-  static __device__ __forceinline__ f32x16 mma(v8 a, v8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kRescaleThr = 8.f;  // deferred online-softmax rescale threshold (log2 units)
 constexpr int FWD_BQ = 128;  // queries per workgroup per q-block of each wave (x QB)
-// keys per tile (FWD_BK), LDS ring depth and workgroups per CU are template parameters
-
-// ---- swizzled LDS images (byte offsets) -------------------------------------------------
-// K: [64 keys][HD] bf16, 16-B chunk c16 of row r stored at chunk c16 ^ swz
-template <int HD> __device__ __forceinline__ int k_off(int r, int c16) {
-  if constexpr (HD == 128) return r * 256 + ((c16 ^ (r & 15)) << 4);
-  else return r * 128 + ((c16 ^ ((r >> 1) & 7)) << 4);
-}
-// V: [64 keys][HD], 64-B chunk c64 (= 32 columns) of row r stored at c64 ^ swz
-template <int HD> __device__ __forceinline__ int v_off(int r, int col) {
-  const int c64 = col >> 5, w = (col & 31) << 1;
-  if constexpr (HD == 128) return r * 256 + ((c64 ^ (r & 3)) << 6) + w;
-  else return r * 128 + ((c64 ^ ((r >> 1) & 1)) << 6) + w;
-}
-
-// two floats -> packed pair (one v_cvt_pk_bf16_f32 for bf16)
-template <typename T> __device__ __forceinline__ uint32_t pack2(float a, float b) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  const t2 v = __builtin_convertvector((f2{a, b}), t2);
-  uint32_t u;
-  __builtin_memcpy(&u, &v, 4);
-  return u;
-}
+constexpr int FWD_NBUF = 2;  // LDS ring slots: the DMA of tile t+1 lands under the MFMAs of tile t
+// keys per tile (FWD_BK) and workgroups per CU are template parameters
 
 // Per 64-key tile and wave: 32 MFMAs, 16 b128 + 32 tr_b64 LDS reads at loop-invariant
 // per-lane offsets, 2x(LD) saddr DMA issues with precomputed per-lane source offsets, and
@@ -87,24 +46,27 @@ template <typename T> __device__ __forceinline__ uint32_t pack2(float a, float b
 // this step's pair of MFMAs, pinned by sched_barrier; PV: the next V^T fragment before each
 // MFMA): hipcc's own schedule waited on every read right before its MFMA (round 6, headline
 // forward +1.5 % same process, profiles/r6/attn/).
-template <typename T, int HD, bool DROP, int FWD_BK, int NBUF, int OCC>
+template <typename T, int HD, bool DROP, int FWD_BK, int OCC>
 __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict__ qkv, T* __restrict__ out,
                                                           float* __restrict__ lse, int T_, int H, int G, int B_,
                                                           bool causal, uint32_t thr, float inv_keep, uint64_t seed,
                                                           uint64_t doff, uint32_t* __restrict__ kmask, int xmap) {
-  typedef typename MF<T>::v8 v8;
+  typedef typename Mma<T>::v8 v8;
   constexpr int KK = HD / 16;               // k-steps of the QK^T product
   constexpr int DT = HD / 32;               // 32-row tiles of O^T
   constexpr int CH = HD / 8;                // 16-B chunks per K/V row
   constexpr int ROWB = HD * 2;
   constexpr int TILE_B = FWD_BK * ROWB;     // bytes per K (or V) tile
   constexpr int LD = FWD_BK * CH / 256;     // 1-KiB pieces per wave per tile (K and V each)
-  constexpr int NPW = 2 * LD;
   constexpr int NKT = FWD_BK / 32;          // 32-key MFMA tiles per step
-  constexpr int QB = 1;                     // 32-query blocks per wave
+  // 32-query blocks per wave.  A constant 1 (file header), yet the block index and its one-trip
+  // loops stay: hipcc's code for this kernel depends on them (without the loops of the Q / O
+  // set-up and of the epilogue it allocates registers and orders blocks differently), and so
+  // does the one-trip loop of the ring prologue below
+  constexpr int QB = 1;
   constexpr int WQ = 32 * QB;               // queries per wave
   constexpr int BQ = FWD_BQ * QB;           // queries per workgroup
-  static_assert(NBUF == 2 || NBUF == 3, "ring depth");
+  constexpr int NBUF = FWD_NBUF;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -165,10 +127,10 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
   // ---- loop-invariant per-lane offsets
   int koff[KK];
 #pragma unroll
-  for (int kk = 0; kk < KK; ++kk) koff[kk] = k_off<HD>(l32, kk * 2 + hh);
+  for (int kk = 0; kk < KK; ++kk) koff[kk] = row_img_off<HD>(l32, kk * 2 + hh);
   int voff[DT];
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) voff[dt] = v_off<HD>(4 * hh + qrow, dt * 32 + gl * 16 + pcol * 4);
+  for (int dt = 0; dt < DT; ++dt) voff[dt] = tr_img_off<HD>(4 * hh + qrow, dt * 32 + gl * 16 + pcol * 4);
   // DMA piece i of this lane: row P / CH, physical 16-B chunk P % CH (P = (w LD + i) 64 + lane);
   // the source chunk carries the image's XOR swizzle.  Recomputed at every issue from an opaque
   // copy of the lane id (kept in VGPRs across the loop they were spilled at hd 128, and each
@@ -180,9 +142,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
     const int P = (w * LD + i) * 64 + ln;
     r = P / CH;
     const int pc = P % CH;
-    if constexpr (HD == 128) kc16 = pc ^ (r & 15); else kc16 = pc ^ ((r >> 1) & 7);
-    const int c64 = (pc >> 2) ^ (HD == 128 ? (r & 3) : ((r >> 1) & 1));
-    vc16 = c64 * 4 + (pc & 3);
+    kc16 = BLLM_ROW_IMG_SRC16(HD, r, pc);
+    vc16 = BLLM_TR_IMG_SRC16(HD, r, pc);
   };
   const uint32_t smem_u = lds_u32(smem);
   // K / V bases in SGPRs once (the per-piece row offsets are then scalar arithmetic)
@@ -210,15 +171,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
       for (int i = 0; i < LD; ++i) {
         const int rb = (w * LD + i) * (64 / CH);
         const uint32_t r = (uint32_t)rb + lr;
-        uint32_t kc16, c64;
-        if constexpr (HD == 128) {
-          kc16 = pc ^ (r & 15u);
-          c64 = (pc >> 2) ^ (r & 3u);
-        } else {
-          kc16 = pc ^ ((r >> 1) & 7u);
-          c64 = (pc >> 2) ^ ((r >> 1) & 1u);
-        }
-        const uint32_t vc16 = c64 * 4u + (pc & 3u);
+        const uint32_t kc16 = BLLM_ROW_IMG_SRC16(HD, r, pc), vc16 = BLLM_TR_IMG_SRC16(HD, r, pc);
         const void* ks = ksb + (long)(k0 + rb) * rs2;
         const void* vs = vsb + (long)(k0 + rb) * rs2;
         const uint32_t pd = (w * LD + i) * 1024;
@@ -238,22 +191,15 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
       }
     }
   };
-  auto ring_wait = [&](int t) {
-    if constexpr (NBUF == 3) {
-      if (t + 2 < ntiles) wait_vm<NPW>(); else wait_vm0();
-    } else {
-      wait_vm0();
-    }
+  // the whole ring is drained at every step: with two slots nothing else is in flight
+  auto ring_wait = [&]() {
+    wait_vm0();
     __builtin_amdgcn_s_barrier();
   };
 #pragma unroll
   for (int j = 0; j < NBUF - 1; ++j)
     if (j < ntiles) issue(j, j);
-  if constexpr (NBUF == 3) {
-    if (ntiles > 1) wait_vm<NPW>(); else wait_vm0();
-  } else {
-    wait_vm0();
-  }
+  wait_vm0();
   __builtin_amdgcn_s_barrier();
   int t = 0, buf = 0;
   // dropout keep-mask words of the last computed tile (kmask != nullptr): stored at the top of
@@ -308,7 +254,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
 #pragma unroll
         for (int kt = 0; kt < NV; ++kt)
 #pragma unroll
-          for (int u = 0; u < QB; ++u) s[u][kt] = MF<T>::mma(cur[kt], qf[u][kk], s[u][kt]);
+          for (int u = 0; u < QB; ++u) s[u][kt] = Mma<T>::mma(cur[kt], qf[u][kk], s[u][kt]);
         __builtin_amdgcn_sched_barrier(0);
         if (kk + 1 < KK) {
 #pragma unroll
@@ -423,9 +369,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
     //      (each V^T fragment feeds QB MFMAs)
     auto vread = [&](int kt, int s2, int dt) {
       const int off = voff[dt] + (kt * 32 + s2 * 16) * ROWB;
-      const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vb + off));
-      const s16x4 r2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vb + off + 8 * ROWB));
-      return __builtin_bit_cast(v8, __builtin_shufflevector(r1, r2, 0, 1, 2, 3, 4, 5, 6, 7));
+      return tr_read8<v8>(vb, off, off + 8 * ROWB);
     };
     {
       // one flat sequence of (kt, s2, dt) MFMAs with the next V^T fragment read before each one
@@ -447,7 +391,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
           }
         }
 #pragma unroll
-        for (int u = 0; u < QB; ++u) o[u][dt] = MF<T>::mma(vcur, pf[u], o[u][dt]);
+        for (int u = 0; u < QB; ++u) o[u][dt] = Mma<T>::mma(vcur, pf[u], o[u][dt]);
         if (i + 1 < NPV) vcur = vnxt;
       }
     }
@@ -467,7 +411,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
     kw_t = t;
     const char* kb = smem + buf * 2 * TILE_B;
     body(IcN{}, No{}, t * FWD_BK, kb, kb + TILE_B);
-    ring_wait(t);  // the DMA of tile t+1 has landed (asm-issued, so drained by hand)
+    ring_wait();  // the DMA of tile t+1 has landed (asm-issued, so drained by hand)
     buf = buf == NBUF - 1 ? 0 : buf + 1;
   }
   // causal diagonal / sequence tail tiles
@@ -480,13 +424,13 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
     const int kvis = min(causal ? wq_hi : T_ - 1, T_ - 1) - k0;  // >= 0 for an active tile
     if (NKT == 1 || kvis >= 32) body(IcN{}, Yes{}, k0, kb, kb + TILE_B);
     else body(Ic1{}, Yes{}, k0, kb, kb + TILE_B);
-    ring_wait(t);
+    ring_wait();
     buf = buf == NBUF - 1 ? 0 : buf + 1;
   }
   flush_mask();
   for (; t < ntiles; ++t) {  // wave done (causal): keep the DMA ring and barriers going
     if (t + NBUF - 1 < ntiles) issue(t + NBUF - 1, buf == 0 ? NBUF - 1 : buf - 1);
-    ring_wait(t);
+    ring_wait();
     buf = buf == NBUF - 1 ? 0 : buf + 1;
   }
 
@@ -497,24 +441,18 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
     // dropout's 1 / keep applied once here instead of to every kept probability
     const float inv = lt > 0.f ? (DROP ? inv_keep : 1.f) / lt : 0.f;
     T* orow = out + ((long)b * T_ + min(qi[u], T_ - 1)) * (long)H * HD + (long)h * HD;
-    // 16-B stores: lane (q, half hh) holds d = 8 gq + 4 hh + 0..3 of each 32-column tile; one
-    // v_permlane32_swap per dword of a (gq, gq+1) pair leaves 8 contiguous d of group gq in the
-    // lower half and of gq+1 in the upper half (cdna_hip_programming.md T21: half the store
-    // instructions of the dwordx2 form, same bytes).  Every lane swaps (cross-lane); only the
-    // store is guarded.
+    // 16-B stores (mma.h pair16): lane (q, half hh) holds d = 8 gq + 4 hh + 0..3 of each
+    // 32-column tile.  Every lane swaps (cross-lane); only the store is guarded.
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int gq = 0; gq < 4; gq += 2) {
-        uint32_t ax = pack2<T>(o[u][dt][4 * gq + 0] * inv, o[u][dt][4 * gq + 1] * inv);
-        uint32_t ay = pack2<T>(o[u][dt][4 * gq + 2] * inv, o[u][dt][4 * gq + 3] * inv);
-        uint32_t bx = pack2<T>(o[u][dt][4 * gq + 4] * inv, o[u][dt][4 * gq + 5] * inv);
-        uint32_t by = pack2<T>(o[u][dt][4 * gq + 6] * inv, o[u][dt][4 * gq + 7] * inv);
-        const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
-        ax = rx[0]; bx = rx[1]; ay = ry[0]; by = ry[1];
-        if (qi[u] < T_)
-          *reinterpret_cast<uint4*>(orow + dt * 32 + 8 * gq + 8 * hh) = uint4{ax, ay, bx, by};
+        const uint32_t lo[2] = {pack2<T>(o[u][dt][4 * gq + 0] * inv, o[u][dt][4 * gq + 1] * inv),
+                               pack2<T>(o[u][dt][4 * gq + 2] * inv, o[u][dt][4 * gq + 3] * inv)};
+        const uint32_t hi[2] = {pack2<T>(o[u][dt][4 * gq + 4] * inv, o[u][dt][4 * gq + 5] * inv),
+                                pack2<T>(o[u][dt][4 * gq + 6] * inv, o[u][dt][4 * gq + 7] * inv)};
+        const uint4 v = pair16(lo, hi);
+        if (qi[u] < T_) *reinterpret_cast<uint4*>(orow + dt * 32 + 8 * gq + 8 * hh) = v;
       }
     if (qi[u] < T_ && hh == 0) lse[((long)b * H + h) * T_ + qi[u]] = m[u] + log2f(lt);
   }
@@ -522,39 +460,36 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_mfma_k(const T* __restrict_
 
 bool attn_mfma_head_dim(int hd) { return hd == 64 || hd == 128; }
 
-// forward tiling: 64-key tiles, 2-slot ring, 2 workgroups per CU; for hd 64 on grids of >= 2048
+// forward tiling: 64-key tiles, 2 workgroups per CU; for hd 64 on grids of >= 2048
 // workgroups 32-key tiles with up to 3 workgroups per CU (GPT2-774M B=24 with dropout 0.179 ->
 // 0.163 ms: the hash work wants the third co-resident workgroup; round 6, after the XCD order:
 // Llama-3.2-1B B=24 without dropout 658 -> 686 TF/s, GPT-2 without dropout unchanged,
 // profiles/r6/attn/smalltiles/).  Dropped: 32-key tiles with a 3-slot ring, two 32-query blocks
 // per wave (slower on every shape, profiles/r3/attn_fwd_qb2.md).
-static bool fwd_small_tiles(int hd, float p, long nwg) {
-  (void)p;
-  return hd == 64 && nwg >= 2048;
-}
+static bool fwd_small_tiles(int hd, long nwg) { return hd == 64 && nwg >= 2048; }
 
 void attn_fwd_mfma(DType dt, const void* qkv, void* o, float* lse, int B, int T_, int H, int G, int hd, bool causal,
                    float p, uint64_t seed, uint64_t offset, uint32_t* keep_mask, hipStream_t s) {
   const uint32_t thr = drop_threshold16(p);
   const float ik = drop_inv_keep(p);
-  const bool small = fwd_small_tiles(hd, p, (long)((T_ + FWD_BQ - 1) / FWD_BQ) * H * B);
+  const bool small = fwd_small_tiles(hd, (long)((T_ + FWD_BQ - 1) / FWD_BQ) * H * B);
   // XCD-aware workgroup order when the (batch, kv head) groups split evenly over the 8 XCDs
   const int xmap = attn_xcd_order_ok(B * H, H / G) ? 1 : 0;
-#define LAUNCH_V(TT, HDD, BK, NB, OC)                                                                      \
+#define LAUNCH_V(TT, HDD, BK, OC)                                                                      \
   do {                                                                                                        \
-    const int lds = NB * 2 * BK * HDD * 2;                                                                    \
+    const int lds = FWD_NBUF * 2 * BK * HDD * 2;                                                                    \
     const dim3 grid(((T_ + FWD_BQ - 1) / FWD_BQ) * H * B), block(256);                                        \
     if (p > 0.f)                                                                                              \
-      hipLaunchKernelGGL((attn_fwd_mfma_k<TT, HDD, true, BK, NB, OC>), grid, block, lds, s,          \
+      hipLaunchKernelGGL((attn_fwd_mfma_k<TT, HDD, true, BK, OC>), grid, block, lds, s,          \
                          (const TT*)qkv, (TT*)o, lse, T_, H, G, B, causal, thr, ik, seed, offset, keep_mask, xmap); \
     else                                                                                                      \
-      hipLaunchKernelGGL((attn_fwd_mfma_k<TT, HDD, false, BK, NB, OC>), grid, block, lds, s,         \
+      hipLaunchKernelGGL((attn_fwd_mfma_k<TT, HDD, false, BK, OC>), grid, block, lds, s,         \
                          (const TT*)qkv, (TT*)o, lse, T_, H, G, B, causal, thr, ik, seed, offset, nullptr, xmap); \
   } while (0)
 #define LAUNCH(TT, HDD)                                                                                       \
   do {                                                                                                        \
-    if (small) LAUNCH_V(TT, HDD, 32, 2, 3);                                                                   \
-    else LAUNCH_V(TT, HDD, 64, 2, 2);                                                                         \
+    if (small) LAUNCH_V(TT, HDD, 32, 3);                                                                   \
+    else LAUNCH_V(TT, HDD, 64, 2);                                                                         \
   } while (0)
   if (dt == DType::BF16) {
     if (hd == 128) LAUNCH(bf16_t, 128); else LAUNCH(bf16_t, 64);

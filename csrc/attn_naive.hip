@@ -12,8 +12,6 @@
 
 namespace bllm {
 
-constexpr float LOG2E = 1.4426950408889634f;
-
 template <typename T, int MAXD>
 __global__ __launch_bounds__(64) void attn_fwd_naive_k(const T* __restrict__ qkv, T* __restrict__ o,
                                                        float* __restrict__ lse, int B, int T_, int H, int G, int hd,
@@ -26,7 +24,7 @@ __global__ __launch_bounds__(64) void attn_fwd_naive_k(const T* __restrict__ qkv
   const int b = (int)(gid / ((long)T_ * H));
   const int g = h / (H / G);
   const long rs = (long)(H + 2 * G) * hd;
-  const float c = rsqrtf((float)hd) * LOG2E;
+  const float c = rsqrtf((float)hd) * kLog2e;
   float qv[MAXD], acc[MAXD];
   const T* qp = qkv + ((long)b * T_ + q) * rs + (long)h * hd;
   for (int i = 0; i < hd; ++i) { qv[i] = to_f(qp[i]) * c; acc[i] = 0.f; }
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_naive_k(const T* __restrict__ 
   const int b = (int)(gid / ((long)T_ * H));
   const int g = h / (H / G);
   const long rs = (long)(H + 2 * G) * hd;
-  const float scale = rsqrtf((float)hd), c = scale * LOG2E;
+  const float scale = rsqrtf((float)hd), c = scale * kLog2e;
   float qv[MAXD], dov[MAXD], dq[MAXD];
   const T* qp = qkv + ((long)b * T_ + q) * rs + (long)h * hd;
   const T* dop = dout + ((long)b * T_ + q) * (long)H * hd + (long)h * hd;
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_naive_k(const T* __restrict__
   const int b = (int)(gid / ((long)T_ * G));
   const int rep = H / G;
   const long rs = (long)(H + 2 * G) * hd;
-  const float scale = rsqrtf((float)hd), c = scale * LOG2E;
+  const float scale = rsqrtf((float)hd), c = scale * kLog2e;
   float kv[MAXD], vv[MAXD], dk[MAXD], dv[MAXD];
   const T* kp = qkv + ((long)b * T_ + k) * rs + (long)(H + g) * hd;
   const T* vp = qkv + ((long)b * T_ + k) * rs + (long)(H + G + g) * hd;

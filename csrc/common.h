@@ -19,6 +19,9 @@ enum class DType : int { F32 = 0, BF16 = 1, F16 = 2 };
 typedef __bf16 bf16_t;
 typedef _Float16 f16_t;
 
+// log2(e): softmax runs on exp2 (v_exp_f32) with the score scale folded into one FMA
+constexpr float kLog2e = 1.4426950408889634f;
+
 template <typename T> __device__ __forceinline__ float to_f(T x) { return static_cast<float>(x); }
 template <typename T> __device__ __forceinline__ T from_f(float x) { return static_cast<T>(x); }
 
@@ -219,6 +222,8 @@ __device__ __forceinline__ void glds4(const void* gsrc, const void* lds_dst) {
                : "=&s"(keep) : "v"(gsrc), "s"(lds) : "memory");
 }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// every LDS (and scalar-memory) op of this wave has completed
+__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // wait until at most N vector-memory ops of this wave are outstanding (prefetch depth > 1)
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 

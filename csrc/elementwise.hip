@@ -5,6 +5,7 @@
 // accesses per lane, grid-stride loops capped at 256 CUs x 8 workgroups.
 #include <cstdlib>
 #include "api.h"
+#include "mma.h"
 
 namespace bllm {
 
@@ -135,33 +136,6 @@ constexpr int LRW_COLS = 64, LRW_CH = 32;
 constexpr int LRW_RS = LRW_COLS * 2 + 16;  // bytes per row of a dg / du / act tile (padded)
 constexpr int LRW_LS = 32;                 // bytes per row of an st / u tile (16 x 16-bit)
 
-typedef short lrw_s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) lrw_s16x4 lrw_lds_s16x4;
-typedef float lrw_f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct LrwMfma;
-template <> struct LrwMfma<bf16_t> {
-  typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ lrw_f32x4 run(v8 a, v8 b, lrw_f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct LrwMfma<f16_t> {
-  typedef _Float16 v8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ lrw_f32x4 run(v8 a, v8 b, lrw_f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
-// 8 k-values (rows 8g .. 8g+7 of a tile) of one column for this lane: two transposed reads
-template <typename v8>
-__device__ __forceinline__ v8 lrw_frag(const char* tile, int stride, int col_byte, int lane) {
-  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-  const char* a = tile + (8 * g + q) * stride + col_byte + 8 * p;
-  const lrw_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lrw_lds_s16x4*)(a));
-  const lrw_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lrw_lds_s16x4*)(a + 4 * stride));
-  return __builtin_bit_cast(v8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 template <typename T>
 __global__ __launch_bounds__(256, 2) void swiglu_bwd_lr_wg_k(const T* __restrict__ gu, const T* __restrict__ base,
                                                           long ldb, const T* __restrict__ u, long ldu,
@@ -169,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void swiglu_bwd_lr_wg_k(const T* __restrict
                                                           long ldst, float s, T* __restrict__ dgu,
                                                           float* __restrict__ part, long N, int F, long rows_per) {
   constexpr int R = 16, VEC = 8;
-  typedef typename LrwMfma<T>::v8 v8;
+  typedef typename Mma<T>::v8 v8;
   __shared__ __attribute__((aligned(16))) char Lt[2][3][LRW_CH * LRW_LS];  // st gate, st up, u
   __shared__ __attribute__((aligned(16))) char Rt[2][3][LRW_CH * LRW_RS];  // dg, du, act
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -208,9 +182,9 @@ __global__ __launch_bounds__(256, 2) void swiglu_bwd_lr_wg_k(const T* __restrict
     if (lq < 3 && row + lrow < r1) lreg = *reinterpret_cast<const uint4*>(pl);
     pg += step_g, pb += step_b, pl += step_l;
   };
-  lrw_f32x4 acc[3];
+  f32x4 acc[3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) acc[q] = lrw_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 3; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (r0 < r1) load(r0);
   int par = 0;
   for (long row = r0; row < r1; row += LRW_CH, par ^= 1) {
@@ -251,9 +225,9 @@ __global__ __launch_bounds__(256, 2) void swiglu_bwd_lr_wg_k(const T* __restrict
     __syncthreads();  // the chunk's dg / du / act tiles visible
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      const v8 a = lrw_frag<v8>(Lt[par][q], LRW_LS, 0, lane);
-      const v8 b = lrw_frag<v8>(Rt[par][q], LRW_RS, 32 * w, lane);
-      acc[q] = LrwMfma<T>::run(a, b, acc[q]);
+      const v8 a = tr_tile8<v8>(Lt[par][q], LRW_LS, 0, lane);
+      const v8 b = tr_tile8<v8>(Rt[par][q], LRW_RS, 32 * w, lane);
+      acc[q] = Mma<T>::mma(a, b, acc[q]);
     }
   }
   // C map of 16x16x32: column = lane & 15, rows 4 (lane >> 4) + i  ->  G_q[j][col]

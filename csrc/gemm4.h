@@ -1,14 +1,12 @@
 // Shared pieces of the 4-wave (one wave per SIMD, 128 x 128 outputs per wave) MFMA GEMMs:
 // csrc/gemm_nt.hip (forward layout) and csrc/gemm_wgrad.hip (weight-gradient layout).
 #pragma once
-#include "common.h"
+#include "mma.h"
 
 namespace bllm {
 namespace g4 {
 
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));  // raw buffer descriptor
 
 constexpr int TN = 256;          // output tile columns (and rows)
 constexpr int THREADS4 = 256;    // 4 waves
@@ -44,9 +42,7 @@ __device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 7\n\ts_nop 7\
 // wave's rows, the tile advance in soffset, m0 written without save / restore (nothing else in the
 // kernel uses m0).  The alternatives measured in round 3 (global_load_lds with saddr, sc0 sc1 and nt
 // cache policies) were no faster and were removed.
-template <int DV>
 __device__ __forceinline__ void bdma16(const i32x4& rsrc, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
-  static_assert(DV == 1, "only the offen descriptor form is kept");
   asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
                ::"v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
 }
@@ -68,13 +64,12 @@ __device__ __forceinline__ void epilogue4(f32x4 (&acc)[8][8], char* smem, int wm
                                           long m0, long n0, long g0, long u0, int accumulate, int wide, OT* act,
                                           int F) {
   OT* cbase = C + m0 * ldc + n0;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkm0();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if constexpr (sizeof(OT) == 2 && EPI == EPI_NONE) {
     if (wide && !accumulate) {
       constexpr int RB = TN * 2;   // 512 B: 32 chunks of 8 elements
-      typedef short s16x4v __attribute__((ext_vector_type(4)));
 #pragma unroll
       for (int I = 0; I < 8; ++I)
 #pragma unroll
@@ -82,12 +77,12 @@ __device__ __forceinline__ void epilogue4(f32x4 (&acc)[8][8], char* smem, int wm
           const int r = 128 * wm + 16 * I + (lane & 15);
           const int col = 128 * wn + 16 * J + 4 * (lane >> 4);          // 4 columns, half a chunk
           const int ch = (col >> 3) ^ (r & 15);
-          s16x4v w;
+          s16x4 w;
 #pragma unroll
           for (int e = 0; e < 4; ++e) w[e] = __builtin_bit_cast(short, from_f<OT>(acc[I][J][e]));
-          *(s16x4v*)(smem + r * RB + ch * 16 + (col & 4) * 2) = w;
+          *(s16x4*)(smem + r * RB + ch * 16 + (col & 4) * 2) = w;
         }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm0();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #pragma unroll 8
@@ -118,7 +113,7 @@ __device__ __forceinline__ void epilogue4(f32x4 (&acc)[8][8], char* smem, int wm
             *(f32x4*)(smem + lr * RB + (((col >> 2) ^ (lr & 7)) << 4)) = acc[I][J];
           }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm0();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #pragma unroll 4
@@ -170,7 +165,7 @@ __device__ __forceinline__ void epilogue4(f32x4 (&acc)[8][8], char* smem, int wm
         }
       }
       if (pass == 0) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }

@@ -32,10 +32,6 @@
 namespace bllm {
 namespace {
 
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x8 lds_s16x8;
-
 constexpr int TM = 256, TN = 256, TK = 64;
 constexpr int ROWB = TK * 2;             // 128 B per LDS row (one K-tile of one row)
 constexpr int IMGB = TM * ROWB;          // 32 KiB per operand image
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(THREADS4, 1) void gemm_nt4p_k(const T* __restrict__
   auto dmap = [&](int buf, int k) {
     const int p = k & 7;
     const uint32_t d = lds0 + (k >= 8 ? 2 * IMGB : 0) + buf * IMGB + (64 * wave + 8 * p) * ROWB;
-    g4::bdma16<1>(k < 8 ? rsA : rsB, k < 8 ? voA[p] : voB[p], soK, d);
+    g4::bdma16(k < 8 ? rsA : rsB, k < 8 ? voA[p] : voB[p], soK, d);
   };
   auto dma = [&](int t, int buf, int k) {   // (prologue)
     dsel(t);
@@ -216,7 +212,7 @@ __global__ __launch_bounds__(THREADS4, 1) void gemm_nt4p_k(const T* __restrict__
       if (n < 16) rd16(a1, b1, cur, 1, n);
       if (n == 2) dsel(t + 2);
       if (n == SC::WAR) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }

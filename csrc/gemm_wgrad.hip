@@ -51,36 +51,6 @@
 namespace bllm {
 namespace {
 
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16_t> {
-  static __device__ __forceinline__ f32x4 run(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                   0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x16 run(s16x8 a, s16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                   0, 0, 0);
-  }
-};
-template <> struct Mfma<f16_t> {
-  static __device__ __forceinline__ f32x4 run(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                  0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x16 run(s16x8 a, s16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                  0, 0, 0);
-  }
-};
-
 constexpr int BM = 256, BN = 256, BK = 32;  // BK = one MFMA k-step per ring slot
 constexpr int NSLOT = 4;
 constexpr int KCH = NSLOT * BK;             // K granule (one trip of the unrolled ring)
@@ -106,13 +76,8 @@ struct Geo {
 
 __device__ __forceinline__ int swz(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
 
-__device__ __forceinline__ s16x8 frag(const char* p) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * ROWB));
-  return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// 8 k-values of one m / n column: k-rows r .. r+3 at p, r+4 .. r+7 four image rows further
+__device__ __forceinline__ s16x8 frag(const char* p) { return tr_read8<s16x8>(p, 0, 4 * ROWB); }
 
 // AK = false: A is [K, M] row-major (token-major dY of a weight gradient; transposed LDS reads).
 // AK = true:  A is [M, K] row-major (K-contiguous, e.g. dY of an input gradient dX = dY W):
@@ -191,7 +156,7 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
                  : rowb + (wm * 16 + ((2 * i) ^ f)) * 16;
   // A fragment: 8 k-values of one m row (row read) or of one m column (two transposed reads)
   auto fragA = [&](const char* p) -> s16x8 {
-    if constexpr (AK) return *(const __attribute__((address_space(3))) s16x8*)(p);
+    if constexpr (AK) return *(const lds_s16x8*)(p);
     else return frag(p);
   };
 #pragma unroll
@@ -226,8 +191,8 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
       constexpr bool STAGE = decltype(do_stage)::value, LAST = decltype(last)::value;
       const char* nxt = smem + ((kt + 1) & (NSLOT - 1)) * SLOTB;
       if constexpr (!LAST) {
-        vm_wait<WAITN>();  // DMA kt+1 landed (later slots may still fly)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // F (= LDS slot kt) is in VGPRs
+        wait_vm<WAITN>();  // DMA kt+1 landed (later slots may still fly)
+        wait_lgkm0();  // F (= LDS slot kt) is in VGPRs
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if constexpr (STAGE) stage(kt + 4, kt & (NSLOT - 1));
@@ -239,7 +204,7 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
         if constexpr (!LAST) Gn.a[i] = fragA(nxt + aoff[i]);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = Mfma<T>::run(F.a[i], F.b[j], acc[i][j]);
+        for (int j = 0; j < FN; ++j) acc[i][j] = Mma<T>::mma(F.a[i], F.b[j], acc[i][j]);
         __builtin_amdgcn_s_setprio(0);
       }
     };
@@ -252,7 +217,7 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
     stage(1, 1);
     stage(2, 2);
     stage(3, 3);
-    vm_wait<3 * PS>();
+    wait_vm<3 * PS>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     Frags F0, F1;
@@ -282,7 +247,7 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
     constexpr int IPR = BN / EPT;              // accesses per row
     constexpr int TRIPS = 128 * IPR / G::THREADS;
     struct alignas(16) V16 { OT e[EPT]; };
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every LDS read of the ring is done
+    wait_lgkm0();  // every LDS read of the ring is done
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 #pragma unroll
@@ -298,7 +263,7 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
               *(float*)(smem + lr * RB + ((((col >> 2) ^ (lr & 7)) << 4) | ((col & 3) << 2))) = acc[i][j][e];
             }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkm0();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #pragma unroll
@@ -324,7 +289,7 @@ __global__ __launch_bounds__(Geo::THREADS) void wgrad_gemm_k(const T* __restrict
         *o = w;
       }
       if (pass == 0) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // pass-0 reads done before pass 1 writes
+        wait_lgkm0();  // pass-0 reads done before pass 1 writes
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
@@ -430,7 +395,7 @@ __global__ __launch_bounds__(g4::THREADS4, 1) void wgrad4_k(const T* __restrict_
     const int p = k & 7, kr = 16 * wave + 2 * p;
     const uint32_t d = lds0 + (k >= 8 ? B_BASE : 0) + (2 * buf + (kr >> 5)) * SLOTB + (kr & 31) * ROWB;
     const T* base = k < 8 ? Abase + (long)t * 64 * lda : Bbase + (long)t * 64 * ldb;
-    g4::bdma16<1>(g4::make_rsrc(base), k < 8 ? voA[p] : voB[p], 0u, d);
+    g4::bdma16(g4::make_rsrc(base), k < 8 ? voA[p] : voB[p], 0u, d);
   };
 
   // ---- fragment offsets (those of wgrad_gemm_k with 128 columns per wave on both operands)
@@ -440,21 +405,21 @@ __global__ __launch_bounds__(g4::THREADS4, 1) void wgrad4_k(const T* __restrict_
   const char* pa = smem + rowb + (wm * 16) * 16;
   const char* pb = smem + B_BASE + rowb + (wn * 16) * 16;
   // i-th 16-column fragment of slot sl: column chunk (2i) ^ f past the wave's base (f < 16, even)
-  auto rdA = [&](int sl, int i) -> g4::s16x8 { return frag(pa + sl * SLOTB + ((2 * i) ^ f) * 16); };
-  auto rdB = [&](int sl, int j) -> g4::s16x8 { return frag(pb + sl * SLOTB + ((2 * j) ^ f) * 16); };
+  auto rdA = [&](int sl, int i) -> s16x8 { return frag(pa + sl * SLOTB + ((2 * i) ^ f) * 16); };
+  auto rdB = [&](int sl, int j) -> s16x8 { return frag(pb + sl * SLOTB + ((2 * j) ^ f) * 16); };
 
-  g4::f32x4 acc[8][8];
+  f32x4 acc[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = g4::f32x4{};
-  g4::s16x8 a0[8], b0[8], a1[8], b1[8];
+    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{};
+  s16x8 a0[8], b0[8], a1[8], b1[8];
 
 #pragma unroll
   for (int k = 0; k < 16; ++k) dma(0, 0, k);
 #pragma unroll
   for (int k = 0; k < 16; ++k) dma(1, 1, k);
-  vm_wait<16>();
+  wait_vm<16>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 #pragma unroll
@@ -471,7 +436,7 @@ __global__ __launch_bounds__(g4::THREADS4, 1) void wgrad4_k(const T* __restrict_
       else if (n <= 8) b1[n - 1] = rdB(2 * cur + 1, n - 1);
       else if (n < 16) a1[n - 8] = rdA(2 * cur + 1, n - 8);
       if (n == 31) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
@@ -483,7 +448,7 @@ __global__ __launch_bounds__(g4::THREADS4, 1) void wgrad4_k(const T* __restrict_
       const int i = n >> 3, j = n & 7;
       if (n >= 3 && n <= 43 && (n - 3) % 5 == 0) dma(tf, cur, 7 + (n - 3) / 5);
       if (n == 48) {
-        vm_wait<16>();
+        wait_vm<16>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
@@ -503,7 +468,7 @@ __global__ __launch_bounds__(g4::THREADS4, 1) void wgrad4_k(const T* __restrict_
     tile(t, I0{});
     tile(t + 1, I1{});
   }
-  vm_wait<0>();
+  wait_vm<0>();
   g4::mfma_drain();
 #pragma unroll
   for (int i = 0; i < 8; ++i)

@@ -21,28 +21,10 @@
 // All three are HBM-bound (the rank is 8-64): x / dy / y are streamed exactly once per kernel
 // with 16-byte lane accesses; the small operands (A, B, t, u) stay L2-resident.
 #include "api.h"
+#include "mma.h"
 
 namespace bllm {
 namespace {
-
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct MF16;
-template <> struct MF16<bf16_t> {
-  static __device__ __forceinline__ f32x4 mma(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                   0, 0, 0);
-  }
-};
-template <> struct MF16<f16_t> {
-  static __device__ __forceinline__ f32x4 mma(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                  0, 0, 0);
-  }
-};
 
 __device__ __forceinline__ s16x8 ld8(const void* p) { return *reinterpret_cast<const s16x8*>(p); }
 
@@ -100,7 +82,7 @@ __global__ __launch_bounds__(256) void lora_down4_k(LoraDownArgs a, int N) {
         for (int u = 0; u < 2; ++u) {
           const s16x8 wb = ld8(w + t * wstep + (ks + u * NW) * 32);
 #pragma unroll
-          for (int rt = 0; rt < RT; ++rt) acc[rt][t] = MF16<T>::mma(xa[u][rt], wb, acc[rt][t]);
+          for (int rt = 0; rt < RT; ++rt) acc[rt][t] = Mma<T>::mma(xa[u][rt], wb, acc[rt][t]);
         }
       }
     }
@@ -114,7 +96,7 @@ __global__ __launch_bounds__(256) void lora_down4_k(LoraDownArgs a, int N) {
       if (t < nt) {
         const s16x8 wb = ld8(w + t * wstep + ks * 32);
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt][t] = MF16<T>::mma(xa[rt], wb, acc[rt][t]);
+        for (int rt = 0; rt < RT; ++rt) acc[rt][t] = Mma<T>::mma(xa[rt], wb, acc[rt][t]);
       }
     }
   }
@@ -241,7 +223,7 @@ __global__ __launch_bounds__(256) void lora_up_k(LoraUpArgs a, int rows, int N) 
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
           const s16x8 ua = live ? *reinterpret_cast<const s16x8*>(&us[(q * 16 + (lane & 15)) * RP + kk]) : zero;
-          acc[q] = MF16<T>::mma(ua, tbv[ks], acc[q]);
+          acc[q] = Mma<T>::mma(ua, tbv[ks], acc[q]);
         }
       }
       // lane holds Y^T[col q*16 + 4(l>>4) + i][row l&15] -> per-wave [16 rows][128 cols] fp32 tile
@@ -287,14 +269,10 @@ __global__ __launch_bounds__(256) void lora_up_k(LoraUpArgs a, int rows, int N) 
 // column-major), two reads per 8-token fragment.  The next chunk's global loads are issued
 // before the current chunk's MFMAs.  Split-N over gridDim.y; with S > 1 each split writes an
 // fp32 partial G that lora_reduce sums in a fixed order (deterministic, no atomics).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
+// rows 0..3 and 4..7 of an 8-row column block (rows of `stride` shorts) -> the 8 k-elements of a
+// 16x16x32 fragment
 __device__ __forceinline__ s16x8 tr_frag(const short* base, int stride) {
-  // rows 0..3 and 4..7 of an 8-row column block -> the 8 k-elements of a 16x16x32 fragment
-  const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base));
-  const s16x4 r2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * stride));
-  return s16x8{r1[0], r1[1], r1[2], r1[3], r2[0], r2[1], r2[2], r2[3]};
+  return tr_read8<s16x8>((const char*)base, 0, 8 * stride);
 }
 
 template <typename T, typename OT>
@@ -347,7 +325,7 @@ __global__ __launch_bounds__(256) void lora_wgrad_k(LoraWgradArgs a, int N) {
       const s16x8 qa = tr_frag(&qs[n * NP + wave * 16 + 4 * tp], NP);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        if (t < nt) acc[t] = MF16<T>::mma(qa, tr_frag(&ps[n * NP + t * 16 + 4 * tp], NP), acc[t]);
+        if (t < nt) acc[t] = Mma<T>::mma(qa, tr_frag(&ps[n * NP + t * 16 + 4 * tp], NP), acc[t]);
     }
   }
   // lane holds G[b = b0 + 16*wave + 4(l>>4) + i][a = 16t + (l&15)]; column tile t of member m
@@ -440,14 +418,6 @@ constexpr int LHB_DS = LHB_SUB * 2 + 16;  // bytes per row of a dl tile (padded)
 constexpr int LHB_SS = 32;                // bytes per row of the st tile
 constexpr int LHB_BS = LHB_SUB * LHB_NSUB * 2 + 16;  // bytes per row of the staged B slab (padded)
 
-__device__ __forceinline__ s16x8 lhb_tr(const char* tile, int stride, int col_byte, int lane) {
-  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-  const char* a = tile + (8 * g + q) * stride + col_byte + 8 * p;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a + 4 * stride));
-  return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 template <typename T, int D>
 __global__ __launch_bounds__(256) void lora_head_bwd_k(const T* __restrict__ dl, long ldl, const T* __restrict__ st,
                                                        long ldst, const T* __restrict__ Bm, long ldb,
@@ -527,14 +497,14 @@ __global__ __launch_bounds__(256) void lora_head_bwd_k(const T* __restrict__ dl,
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
             // dB: [16 j x 16 cols of wave w] += st^T [16 x 32 rows] . dl [32 rows x 16 cols]
-            const s16x8 a = lhb_tr(St + ks * 32 * LHB_SS, LHB_SS, 0, lane);
-            const s16x8 b = lhb_tr(Dt[par] + ks * 32 * LHB_DS, LHB_DS, 32 * w, lane);
-            accB[sub] = MF16<T>::mma(a, b, accB[sub]);
+            const s16x8 a = tr_tile8<s16x8>(St + ks * 32 * LHB_SS, LHB_SS, 0, lane);
+            const s16x8 b = tr_tile8<s16x8>(Dt[par] + ks * 32 * LHB_DS, LHB_DS, 32 * w, lane);
+            accB[sub] = Mma<T>::mma(a, b, accB[sub]);
             // u: [16 rows of wave w x 16 j] += dl [16 rows x 32 cols] . B^T [32 cols x 16 j]
             const int k8 = 32 * ks + 8 * (lane >> 4);
             const s16x8 ua = *reinterpret_cast<const s16x8*>(Dt[par] + (16 * w + (lane & 15)) * LHB_DS + 2 * k8);
             const s16x8 ub = *reinterpret_cast<const s16x8*>(Bs + (lane & 15) * LHB_BS + 2 * (sub * LHB_SUB + k8));
-            accU = MF16<T>::mma(ua, ub, accU);
+            accU = Mma<T>::mma(ua, ub, accU);
           }
           par ^= 1;
         }
