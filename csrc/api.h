@@ -238,7 +238,8 @@ void gemm_nt_swiglu(DType dt, const void* a, long lda, const void* w, long ldw, 
 
 // optim.hip
 void adamw_step(DType pdt, DType gdt, void* param, float* master, const void* grad, float* m, float* v, long n,
-                float lr, float b1, float b2, float eps, float wd, int step, const float* gscale, hipStream_t s);
+                double lr, double b1, double b2, double eps, double wd, int step, const float* gscale,
+                hipStream_t s);
 int sqsum_slots(long n);
 void sqsum_partial(DType dt, const void* x, long n, float* part, int slots, hipStream_t s);
 void sum_partials(const float* part, int n, float* out, hipStream_t s);

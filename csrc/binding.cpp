@@ -1034,8 +1034,7 @@ void adamw_step_(Tensor& param, const optional<Tensor>& master, const Tensor& gr
     gs = grad_scale->data_ptr<float>();
   }
   bllm::adamw_step(dt_of(param), dt_of(grad), param.data_ptr(), mp, grad.data_ptr(), exp_avg.data_ptr<float>(),
-                   exp_avg_sq.data_ptr<float>(), n, (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
-                   (int)step, gs, stream());
+                   exp_avg_sq.data_ptr<float>(), n, lr, b1, b2, eps, wd, (int)step, gs, stream());
 }
 
 }  // namespace

@@ -48,12 +48,10 @@ __device__ __forceinline__ void stnt(T* p, const VecN<T, N>& r) {
 template <typename P, typename G, int VEC, int UNROLL>
 __global__ __launch_bounds__(256) void adamw_k(P* __restrict__ param, float* __restrict__ master,
                                                const G* __restrict__ grad, float* __restrict__ m,
-                                               float* __restrict__ v, long nvec, float lr, float b1, float b2,
-                                               float eps, float wd, float bc1, float bc2_sqrt,
+                                               float* __restrict__ v, long nvec, float b1, float omb1, float b2,
+                                               float omb2, float eps, float decay, float step, float bc2_sqrt,
                                                const float* __restrict__ gscale) {
   const float gs = gscale ? gscale[0] : 1.f;
-  const float decay = 1.f - lr * wd;
-  const float step = lr / bc1;
   const long stride = (long)gridDim.x * 256 * UNROLL;
   for (long i0 = blockIdx.x * 256L * UNROLL + threadIdx.x; i0 < nvec; i0 += stride) {
     VecN<G, VEC> gv[UNROLL];
@@ -83,8 +81,8 @@ __global__ __launch_bounds__(256) void adamw_k(P* __restrict__ param, float* __r
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
           const float g = to_f(gv[u].v[j]) * gs;
-          mv[u].v[j] = b1 * mv[u].v[j] + (1.f - b1) * g;
-          vv[u].v[j] = b2 * vv[u].v[j] + (1.f - b2) * g * g;
+          mv[u].v[j] = b1 * mv[u].v[j] + omb1 * g;
+          vv[u].v[j] = b2 * vv[u].v[j] + omb2 * g * g;
           float p = pv[u].v[j] * decay;
           p -= step * mv[u].v[j] / (sqrtf(vv[u].v[j]) / bc2_sqrt + eps);
           pv[u].v[j] = p;
@@ -137,28 +135,35 @@ __global__ __launch_bounds__(256) void sum_k(const float* __restrict__ part, int
 }
 
 template <typename P, typename G>
-static void adamw_launch(void* param, float* master, const void* grad, float* m, float* v, long n, float lr,
-                         float b1, float b2, float eps, float wd, float bc1, float bc2s, const float* gscale,
-                         hipStream_t s) {
+static void adamw_launch(void* param, float* master, const void* grad, float* m, float* v, long n, float b1,
+                         float omb1, float b2, float omb2, float eps, float decay, float step, float bc2s,
+                         const float* gscale, hipStream_t s) {
   if (n % 4 == 0) {
     long nv = n / 4;
     int g = (int)((nv + 511) / 512 < 2048 ? (nv + 511) / 512 : 2048);
     hipLaunchKernelGGL((adamw_k<P, G, 4, 2>), dim3(g > 0 ? g : 1), dim3(256), 0, s, (P*)param, master,
-                       (const G*)grad, m, v, nv, lr, b1, b2, eps, wd, bc1, bc2s, gscale);
+                       (const G*)grad, m, v, nv, b1, omb1, b2, omb2, eps, decay, step, bc2s, gscale);
   } else {
     int g = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL((adamw_k<P, G, 1, 1>), dim3(g > 0 ? g : 1), dim3(256), 0, s, (P*)param, master,
-                       (const G*)grad, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, gscale);
+                       (const G*)grad, m, v, n, b1, omb1, b2, omb2, eps, decay, step, bc2s, gscale);
   }
 }
 
+// The scalars derived from the hyper-parameters (1 - beta, the decay factor, the bias corrections)
+// are formed here in double and rounded once: 1.f - (float)0.999 is 1.3e-5 (relative) away from
+// 0.001, and powf(0.999f, 1000) as far from 0.999^1000 -- errors that reach the update of an
+// element whose second moment is small at several times the fp32 rounding of the parameter.
 void adamw_step(DType pdt, DType gdt, void* param, float* master, const void* grad, float* m, float* v, long n,
-                float lr, float b1, float b2, float eps, float wd, int step, const float* gscale, hipStream_t s) {
-  const float bc1 = 1.f - powf(b1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(b2, (float)step));
+                double lr, double b1, double b2, double eps, double wd, int step, const float* gscale,
+                hipStream_t s) {
+  const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2);
+  const float decay = (float)(1.0 - lr * wd);
+  const float stepsz = (float)(lr / (1.0 - pow(b1, (double)step)));
+  const float bc2s = (float)sqrt(1.0 - pow(b2, (double)step));
   BLLM_DISPATCH(pdt, P, {
-    BLLM_DISPATCH(gdt, G, (adamw_launch<P, G>(param, master, grad, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s,
-                                              gscale, s)));
+    BLLM_DISPATCH(gdt, G, (adamw_launch<P, G>(param, master, grad, m, v, n, (float)b1, omb1, (float)b2, omb2,
+                                              (float)eps, decay, stepsz, bc2s, gscale, s)));
   });
 }
 
