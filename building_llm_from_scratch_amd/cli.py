@@ -27,6 +27,8 @@ logger = setup_logger("main")
 def perform_checks(args):
     if not args.warnings:
         warnings.filterwarnings("ignore")
+    if getattr(args, "unpad", False) and not (args.finetune and str(args.model).lower().startswith("llama")):
+        raise ValueError("--unpad needs --finetune and a Llama model (GPT-2 is not supported).")
     if not os.path.exists(args.data_dir):
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -132,6 +134,9 @@ def build_parser() -> argparse.ArgumentParser:
     x.add_argument("--tunableop", type=str, default="auto",
                    help="TunableOp GEMM table (read-only): a CSV path, 'auto' = the shipped MI355X table of "
                         "--model/--num_params if there is one (configs/tunableop_*), or 'none'")
+    x.add_argument("--unpad", action="store_true",
+                   help="instruction finetuning (Llama): run only each record's real rows, not the positions "
+                        "the collate padded to the longest record (same loss and gradients)")
     x.add_argument("--no_plot", action="store_true")
     x.add_argument("--skip_final_save", action="store_true",
                    help="do not write model_pg_final.pth (throughput runs of multi-GB models)")
@@ -243,7 +248,8 @@ def main(rank: int, args):
                       loss_scaler=DynamicLossScaler() if config.dtype == torch.float16 else None,
                       max_steps=args.max_steps, sample_tokens=args.sample_tokens,
                       save_resume=args.save_resume_state, world_size=world, profile_steps=args.profile_steps,
-                      num_workers=args.num_workers, seed=args.seed, comm_adapt_steps=args.comm_adapt_steps)
+                      num_workers=args.num_workers, seed=args.seed, comm_adapt_steps=args.comm_adapt_steps,
+                      unpad=args.unpad)
     trainer.generate_and_print_sample("Every effort moves you", temperature=1.0, top_k=5, memory_check=True)
     if args.resume:
         # after the start-up sample: the restored host RNG state is the one saved at the checkpoint

@@ -141,6 +141,17 @@ class InstructionDatasetPhi(Dataset):
         return len(self.data)
 
 
+def unpad_lengths(targets: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+    """Real length of each row of a collated target batch [B, T]: the index of its last
+    non-ignored target + 1, 0 for a fully ignored row -> LongTensor [B] on the CPU.  Positions
+    past it cannot reach the loss (their targets are ignored and causal attention lets no
+    earlier token see them)."""
+    t = targets.detach().cpu()
+    valid = t != ignore_index
+    last = (valid * torch.arange(1, t.shape[1] + 1)).amax(dim=1) if t.shape[1] else valid.sum(dim=1)
+    return last.to(torch.long)
+
+
 def custom_collate_fn(batch, pad_token_id: int = 50256, ignore_index: int = -100,
                       allowed_max_length: Optional[int] = None):
     batch_max_length = max(len(item) + 1 for _, item in batch)

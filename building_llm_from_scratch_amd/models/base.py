@@ -97,6 +97,9 @@ class RunCtx:
         self.rope = None               # (cos, sin) fp32 [T, hd/2] on device
         self.B = 1
         self.T = 1
+        # unpadded forward (``model(idx, targets, seq_lens=...)``): the packed batch's SeqPack, valid
+        # through that step's backward and checkpoint recompute like B / T; None on the padded path
+        self.seq: Optional["SeqPack"] = None
         self.profile_hook = None
         # unit index -> HIP event recorded after that unit's optimizer update (the update
         # runs on a side stream, overlapped with the next forward; see train/optim.py)
@@ -131,6 +134,52 @@ class RunCtx:
     @property
     def drop_p(self) -> float:
         return float(self.cfg.drop_rate) if self.training else 0.0
+
+
+class SeqPack:
+    """A batch compacted to its real rows: sequence b is rows [bounds[b], bounds[b+1]) of the
+    packed [N, ...] activations.  Built on the host once per forward (``pack_sequences``)."""
+
+    def __init__(self, sel, pos, bounds, device):
+        self.sel = sel                                  # LongTensor: flat (b * T + t) index of each real row
+        self.bounds = bounds                            # host list [nseq + 1], bounds[-1] = N (pad sequences included)
+        self.N = bounds[-1]
+        self.max_len = max(b - a for a, b in zip(bounds[:-1], bounds[1:]))
+        self.cu = torch.tensor(bounds, dtype=torch.int32).to(device, non_blocking=True)
+        self.pos_ids = pos.to(torch.int32).to(device, non_blocking=True)   # each row's index in its sequence
+
+
+def pack_sequences(in_idx: torch.Tensor, targets: torch.Tensor, seq_lens, row_multiple: int, device,
+                   ignore_index: int = -100):
+    """Compact ``in_idx`` / ``targets`` [B, T] to rows (b, 0 .. seq_lens[b] - 1) in batch order ->
+    (idx [1, N], targets [N], SeqPack).  N is rounded up to ``row_multiple`` (a whole multiple
+    even when no row is real): the extra rows are token 0 with ignored targets and form further
+    sequences of at most T rows each (one, whenever they fit the row length), so their positions
+    stay inside the RoPE table; they get a zero logit gradient and add exactly 0 to every dX / dW."""
+    B, T = in_idx.shape
+    lens = torch.as_tensor(seq_lens, dtype=torch.long, device="cpu").reshape(-1)
+    if lens.numel() != B or (B and (int(lens.min()) < 0 or int(lens.max()) > T)):
+        raise ValueError(f"seq_lens must hold {B} lengths in [0, {T}]")
+    if targets.shape != in_idx.shape:
+        raise ValueError("seq_lens needs targets of the input's shape [B, T]")
+    ar = torch.arange(T)
+    mask = ar[None, :] < lens[:, None]
+    sel = mask.reshape(-1).nonzero().squeeze(1)
+    pos = ar.expand(B, T)[mask]
+    n = int(sel.numel())
+    bounds = [0] + torch.cumsum(lens, 0).tolist()
+    pad = (-n) % row_multiple if n else row_multiple
+    while pad:
+        step = min(pad, T)
+        bounds.append(bounds[-1] + step)
+        pos = torch.cat([pos, torch.arange(step)])
+        pad -= step
+    npad = bounds[-1] - n
+    idx = in_idx.reshape(-1)[sel.to(in_idx.device)]
+    tg = targets.reshape(-1)[sel.to(targets.device)]
+    idx = torch.cat([idx, idx.new_zeros(npad)]).view(1, -1)
+    tg = torch.cat([tg, tg.new_full((npad,), ignore_index)])
+    return idx, tg, SeqPack(sel, pos, bounds, device)
 
 
 class UnitCompute:
@@ -424,11 +473,25 @@ class BaseLM(nn.Module):
         return r
 
     # -- forward -----------------------------------------------------------------------
+    def _pack(self, in_idx, targets, seq_lens):
+        """(idx, targets, SeqPack) of an unpadded forward; models that support it override."""
+        raise NotImplementedError(f"seq_lens is not supported by {type(self).__name__} (Llama models only: GPT-2 "
+                                  "needs learned position ids and attention dropout)")
+
     def forward(self, in_idx: torch.Tensor, targets: Optional[torch.Tensor] = None,
-                last_only: bool = False):
+                last_only: bool = False, seq_lens=None):
+        """``seq_lens`` (CPU integer tensor or list [B], 0 <= len_b <= T; needs ``targets``): run
+        only rows 0 .. len_b - 1 of each sequence -- the trailing positions of a collated
+        instruction batch, whose targets are all ignored, cost nothing.  Same loss and gradients
+        as the padded call (mean over the non-ignored targets)."""
         self._ensure_flat()
         comps = self._comps
         rc = self._rctx
+        rc.seq = None
+        if seq_lens is not None:
+            if targets is None:
+                raise ValueError("seq_lens needs targets: the unpadded forward computes the loss, not logits")
+            in_idx, targets, rc.seq = self._pack(in_idx, targets, seq_lens)
         B, T = in_idx.shape
         rc.B, rc.T = B, T
         idx = in_idx.to(self._anchor.device, non_blocking=True)

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .base import BaseLM, UnitCompute, cached_attention
+from .base import BaseLM, UnitCompute, cached_attention, pack_sequences
 from .linear import FusedLinear, _dgrad_wt_ok, _weight_grad, mm_nt
 
 
@@ -156,6 +156,7 @@ class LlamaBlockCompute(UnitCompute):
         H, G, hd = cfg.n_heads, cfg.n_kv_groups, cfg.head_dim
         eps = cfg.norm_eps
         cos, sin = rc.rope
+        sq = rc.seq
         x2d = x.reshape(N, d)
         keep = rc.block_mode(self.index) == "none" or recompute  # the recompute's outputs live one block
         # LoRA with a frozen base: the norms / SwiGLU write straight into the K-augmented
@@ -164,16 +165,20 @@ class LlamaBlockCompute(UnitCompute):
         if xq is not None:
             h1, r1 = ops.rmsnorm_fwd_into(x2d, u.data(b.norm1.weight), eps, xq[:, :d])
             qkv, xa_qkv = self.qkv.forward_kaug(xq, d)
-            ops.rope_(qkv, cos, sin, T, H, G, hd)
+            self._rope(qkv)
         else:
             h1, r1 = ops.rmsnorm_fwd(x2d, u.data(b.norm1.weight), eps)
-            qkv = self.qkv.forward_rope(h1, cos, sin, T, H, G, hd)   # K4: RoPE in the GEMM epilogue
+            # K4: RoPE in the GEMM epilogue (position = row % T: not for a packed batch)
+            qkv = self.qkv.forward_rope(h1, cos, sin, T, H, G, hd) if sq is None else None
             if qkv is not None:
                 xa_qkv = None
             else:
                 qkv, xa_qkv = self.qkv.forward(h1)
-                ops.rope_(qkv, cos, sin, T, H, G, hd)
-        o, lse = ops.flash_attn_fwd(qkv, B, T, H, G, hd, causal=True)
+                self._rope(qkv)
+        if sq is not None:   # packed batch: sequence b is rows [cu[b], cu[b+1])
+            o, lse = ops.flash_attn_varlen_fwd(qkv, sq.cu, sq.max_len, H, G, hd, bounds=sq.bounds)
+        else:
+            o, lse = ops.flash_attn_fwd(qkv, B, T, H, G, hd, causal=True)
         x2, xa_o = self.o.forward(o, residual=x2d)
         xg = self.gu.kaug_input(x2, d)
         fused = None
@@ -218,6 +223,14 @@ class LlamaBlockCompute(UnitCompute):
             if keep:
                 saved.update(h1=h1, h2=h2)
         return (x3.view(B, T, d) if x3 is not None else None), saved
+
+    def _rope(self, qkv):
+        """RoPE in place: position row % T, or each row's index in its sequence (packed batch)."""
+        rc, cfg = self.rctx, self.rctx.cfg
+        cos, sin = rc.rope
+        if rc.seq is not None:
+            return ops.rope_pos_(qkv, cos, sin, rc.seq.pos_ids, cfg.n_heads, cfg.n_kv_groups, cfg.head_dim)
+        return ops.rope_(qkv, cos, sin, rc.T, cfg.n_heads, cfg.n_kv_groups, cfg.head_dim)
 
     def infer_dev(self, x2d, pos_t, kv):
         """Decode step with the position in device memory (RoPE reads it, the decode kernel
@@ -313,8 +326,13 @@ class LlamaBlockCompute(UnitCompute):
         del dh2
         # ---- attention
         d_o = self.o.backward(dx2, s["o"], xa_o, accumulate=acc)
-        dqkv = ops.flash_attn_bwd(s["qkv"], s["o"], s["lse"], d_o, B, T, H, G, hd, causal=True,
-                                  rope=(cos, sin))  # inverse RoPE fused into the kernels' epilogues
+        sq = rc.seq
+        if sq is not None:
+            dqkv = ops.flash_attn_varlen_bwd(s["qkv"], s["o"], s["lse"], d_o, sq.cu, sq.pos_ids, sq.max_len, H, G, hd,
+                                             rope=(cos, sin), bounds=sq.bounds)
+        else:
+            dqkv = ops.flash_attn_bwd(s["qkv"], s["o"], s["lse"], d_o, B, T, H, G, hd, causal=True,
+                                      rope=(cos, sin))  # inverse RoPE fused into the kernels' epilogues
         del d_o
         h1 = s["h1"] if "h1" in s else ops.rmsnorm_fwd(s["x"], w1, eps)[0]
         dh1 = self.qkv.backward(dqkv, h1, xa_qkv, accumulate=acc)
@@ -621,6 +639,11 @@ class LlamaModel(BaseLM):
         return ([LlamaEmbedCompute(rc, self)]
                 + [LlamaBlockCompute(rc, b, i) for i, b in enumerate(self.trf_blocks)]
                 + [LlamaHeadCompute(rc, self)])
+
+    def _pack(self, in_idx, targets, seq_lens):
+        # whole MIN_CHUNK_ROWS row counts keep every weight gradient on the token-major dW kernel
+        return pack_sequences(in_idx, targets, seq_lens, MIN_CHUNK_ROWS, self._anchor.device,
+                              self.computes[-1].ignore_index)
 
     def _after_flatten(self, device):
         cfg = self.cfg

@@ -22,7 +22,8 @@ from ._ext import ext_available, kernel_debug, load_ext
 __all__ = [
     "rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "dropout_add", "dropout_bwd",
     "dropout_add_layernorm",
-    "rope_", "rope_tables", "flash_attn_fwd", "flash_attn_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
+    "rope_", "rope_pos_", "rope_tables", "flash_attn_fwd", "flash_attn_bwd", "flash_attn_varlen_fwd",
+    "flash_attn_varlen_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
     "swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank_wgrad_ok",
     "gelu_fwd", "gelu_bwd", "gelu_bwd_bias", "gelu_bwd_act", "dropout_bwd_bias", "ce_fwd", "ce_bwd_", "embedding_fwd", "embedding_bwd",
     "sq_norm_multi", "adamw_step_", "attn_decode", "bias_grad_", "ext_available", "load_ext", "attention_backend",
@@ -189,6 +190,53 @@ def rope_(qkv, cos, sin, T: int, H: int, G: int, hd: int, inverse: bool = False,
         _k().rope_(qkv, cos, sin, T, H, G, hd, inverse, pos_offset)
         return qkv
     return ref.rope_(qkv, cos, sin, T, H, G, hd, inverse, pos_offset)
+
+
+def rope_pos_(qkv, cos, sin, pos_ids, H: int, G: int, hd: int, inverse: bool = False):
+    """``rope_`` of a packed variable-length batch: row r rotated at ``pos_ids[r]`` (int32 [N], its
+    index inside its sequence)."""
+    if _hip(qkv):
+        _k().rope_pos_(qkv, cos, sin, pos_ids, H, G, hd, inverse)
+        return qkv
+    return ref.rope_pos_(qkv, cos, sin, pos_ids, H, G, hd, inverse)
+
+
+def _varlen_kernel(qkv, hd: int) -> bool:
+    return qkv.dtype in (torch.bfloat16, torch.float16) and hd in (64, 128)
+
+
+def flash_attn_varlen_fwd(qkv, cu, max_len: int, H: int, G: int, hd: int, bounds=None):
+    """Causal attention over a packed batch without padding: sequence b is rows
+    [cu[b], cu[b+1]) of qkv [N, (H+2G)*hd] (``cu`` int32 [B + 1] on qkv's device, ``max_len`` >=
+    every length) -> (o [N, H*hd], lse [H * N] fp32).  bf16 / fp16 with head dim 64 / 128 run the
+    variable-length MFMA kernels; any other GPU dtype or head dim runs the uniform op once per
+    sequence on its row slice (``bounds``: ``cu`` as a host list, saves reading it back); CPU
+    tensors go to the oracle."""
+    if qkv.device.type == "cuda":
+        load_ext(required=True)
+        if _varlen_kernel(qkv, hd):
+            return _k().flash_attn_varlen_fwd(qkv, cu, int(max_len), H, G, hd)
+        return ref.flash_attn_varlen_fwd(qkv, cu if bounds is None else bounds, max_len, H, G, hd,
+                                         attn=flash_attn_fwd)
+    return ref.flash_attn_varlen_fwd(qkv, cu if bounds is None else bounds, max_len, H, G, hd)
+
+
+def flash_attn_varlen_bwd(qkv, o, lse, do, cu, pos_ids, max_len: int, H: int, G: int, hd: int, rope=None,
+                          bounds=None):
+    """Backward of ``flash_attn_varlen_fwd`` -> dqkv.  ``rope``: the (cos, sin) tables the forward
+    rotated q / k with (``rope_pos_`` at ``pos_ids``); dq / dk then come back un-rotated."""
+    if qkv.device.type == "cuda":
+        load_ext(required=True)
+        if _varlen_kernel(qkv, hd):
+            rc, rs = rope if rope is not None else (None, None)
+            return _k().flash_attn_varlen_bwd(qkv, o, lse, do, cu, pos_ids, int(max_len), H, G, hd, rc, rs)
+        dqkv = ref.flash_attn_varlen_bwd(qkv, o, lse, do, cu if bounds is None else bounds, pos_ids, max_len, H, G,
+                                         hd, None, attn_bwd=flash_attn_bwd)
+        if rope is not None:
+            rope_pos_(dqkv, rope[0], rope[1], pos_ids, H, G, hd, inverse=True)
+        return dqkv
+    return ref.flash_attn_varlen_bwd(qkv, o, lse, do, cu if bounds is None else bounds, pos_ids, max_len, H, G, hd,
+                                     rope)
 
 
 def attention_backend(dtype: torch.dtype, device_type: str = "cuda") -> str:

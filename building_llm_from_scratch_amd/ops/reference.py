@@ -161,6 +161,21 @@ def rope_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, T: int, n_hea
     return qkv
 
 
+def rope_pos_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_ids: torch.Tensor, n_heads: int,
+              n_kv: int, head_dim: int, inverse: bool = False) -> torch.Tensor:
+    """``rope_`` of a packed variable-length batch: row r is rotated at ``pos_ids[r]``.  Each run
+    of consecutive positions 0, 1, 2, ... is one sequence and goes through ``rope_``."""
+    pos = [int(p) for p in pos_ids.tolist()]
+    r = 0
+    while r < len(pos):
+        e = r + 1
+        while e < len(pos) and pos[e] == pos[e - 1] + 1:
+            e += 1
+        rope_(qkv[r:e], cos, sin, e - r, n_heads, n_kv, head_dim, inverse, pos_offset=pos[r])
+        r = e
+    return qkv
+
+
 # ---------------------------------------------------------------------------
 # attention on the packed qkv buffer
 # ---------------------------------------------------------------------------
@@ -196,6 +211,46 @@ def flash_attn_fwd(qkv, B: int, T: int, H: int, G: int, hd: int, causal: bool = 
         p = p * keep * drop_inv_keep(dropout_p)
     o = (p @ v).permute(0, 2, 1, 3).reshape(B * T, H * hd).to(qkv.dtype)
     return o, lse * (1.0 / math.log(2.0))
+
+
+def varlen_bounds(cu) -> list:
+    """Host row offsets [B + 1] of a packed variable-length batch from ``cu`` (tensor or list)."""
+    return [int(c) for c in (cu.tolist() if isinstance(cu, torch.Tensor) else cu)]
+
+
+def flash_attn_varlen_fwd(qkv, cu, max_len: int, H: int, G: int, hd: int, attn=None):
+    """Causal attention over a packed batch: sequence b is rows [cu[b], cu[b+1]) of qkv
+    [N, (H+2G)*hd].  Returns o [N, H*hd] and lse [H * N] fp32 (log2 units), the [H, len_b] block
+    of sequence b at H * cu[b].  One call of ``attn`` (default: ``flash_attn_fwd`` above) per
+    sequence on its row slice."""
+    attn = attn or flash_attn_fwd
+    cb = varlen_bounds(cu)
+    N = qkv.shape[0]
+    o = torch.zeros(N, H * hd, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.zeros(H * N, dtype=torch.float32, device=qkv.device)
+    for r0, r1 in zip(cb[:-1], cb[1:]):
+        if r1 > r0:
+            ob, lb = attn(qkv[r0:r1], 1, r1 - r0, H, G, hd, True)
+            o[r0:r1] = ob
+            lse[H * r0:H * r1] = lb.reshape(-1)
+    return o, lse
+
+
+def flash_attn_varlen_bwd(qkv, o, lse2, do, cu, pos_ids, max_len: int, H: int, G: int, hd: int, rope=None,
+                          attn_bwd=None):
+    """Backward of ``flash_attn_varlen_fwd`` -> dqkv [N, (H+2G)*hd]; with ``rope`` = (cos, sin)
+    dq / dk come back un-rotated at the positions ``pos_ids`` (each row's index in its sequence)."""
+    attn_bwd = attn_bwd or flash_attn_bwd
+    cb = varlen_bounds(cu)
+    dqkv = torch.zeros_like(qkv)
+    for r0, r1 in zip(cb[:-1], cb[1:]):
+        if r1 > r0:
+            L = r1 - r0
+            dqkv[r0:r1] = attn_bwd(qkv[r0:r1], o[r0:r1], lse2[H * r0:H * r1].view(1, H, L), do[r0:r1], 1, L, H, G,
+                                   hd, True)
+    if rope is not None:
+        rope_pos_(dqkv, rope[0], rope[1], pos_ids, H, G, hd, inverse=True)
+    return dqkv
 
 
 def flash_attn_bwd(qkv, o, lse2, do, B: int, T: int, H: int, G: int, hd: int, causal: bool = True,

@@ -28,6 +28,7 @@ import torch.distributed as dist
 
 from ..logger import MetricsWriter, setup_logger
 from ..utils.misc import read_json_file, read_text_file, text_to_token_ids, token_ids_to_text
+from ..data.datasets import unpad_lengths
 from ..data.loaders import first_batches
 from .checkpoint import resume_state_path, save_model, save_resume_state
 from .generate import generate_cached
@@ -80,8 +81,11 @@ class Trainer:
                  loss_scaler: Optional[DynamicLossScaler] = None, max_steps: Optional[int] = None,
                  sample_tokens: int = 200, save_resume: bool = False, world_size: int = 1,
                  profile_steps: Optional[str] = None, num_workers: int = 0, seed: int = 123,
-                 comm_adapt_steps: int = 3):
+                 comm_adapt_steps: int = 3, unpad: bool = False):
         self.config = config
+        # instruction finetuning on a Llama model: run only each row's real positions (those up to
+        # its last non-ignored target) -- same loss and gradients, none of the padding's work
+        self.unpad = bool(unpad)
         self.model = model
         self.optimizer = optimizer
         self.data_files = data_files
@@ -174,6 +178,9 @@ class Trainer:
 
     # ------------------------------------------------------------------ steps
     def calc_loss_batch(self, input_batch, target_batch):
+        if self.unpad:
+            # lengths and the packing from the host tensors: only the real rows are copied over
+            return self.model(input_batch, target_batch, seq_lens=unpad_lengths(target_batch))
         input_batch = input_batch.to(self.device, non_blocking=True)
         target_batch = target_batch.to(self.device, non_blocking=True)
         return self.model(input_batch, target_batch)

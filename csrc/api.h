@@ -57,6 +57,9 @@ void dropout_add(DType dt, const void* x, const void* a, void* out, long n, floa
                  hipStream_t s);
 void rope(DType dt, void* qkv, const float* cosT, const float* sinT, long N, int T, int H, int G, int hd,
           bool inverse, int pos_offset, hipStream_t s, const int* pos_dev = nullptr);
+// packed variable-length batches: row r rotated at pos_ids[r] (device int32 [N])
+void rope_pos(DType dt, void* qkv, const float* cosT, const float* sinT, const int* pos_ids, long N, int H, int G,
+              int hd, bool inverse, hipStream_t s);
 
 // bias gradient (column sums): part must hold colsum_bands(N, F) * F floats
 int colsum_bands(int N, int F);
@@ -88,6 +91,12 @@ bool attn_mfma_head_dim(int hd);
 void attn_fwd_mfma(DType dt, const void* qkv, void* o, float* lse, int B, int T, int H, int G, int hd, bool causal,
                    float p, uint64_t seed, uint64_t offset, uint32_t* keep_mask, hipStream_t s);
 
+// variable-length form (causal, no dropout): sequence b is rows [cu[b], cu[b+1]) of the packed
+// qkv / o (cu: device int32 [B + 1], cu[B] = N), max_len >= every length; lse is [H * N] floats
+// at H cu[b] + h len_b + q
+void attn_fwd_mfma_varlen(DType dt, const void* qkv, void* o, float* lse, const int* cu, int B, int max_len, int H,
+                          int G, int hd, hipStream_t s);
+
 // attn_bwd_mfma.hip: its backward (inverse RoPE of dQ / dK fused into the epilogues when rcos is set)
 // whether the dK/dV pass needs the fp32 per-head partial buffer (GQA without the fused-head variant)
 bool attn_bwd_kv_partials(int B, int T, int H, int G);
@@ -95,6 +104,12 @@ void attn_bwd_mfma(DType dt, const void* qkv, const void* o, const float* lse, c
                    float* delta, float* dkv_part, int B, int T, int H, int G, int hd, bool causal, float p,
                    uint64_t seed, uint64_t offset, const uint32_t* keep_mask, const float* rcos, const float* rsin,
                    hipStream_t s);
+// variable-length form: delta [H * N] floats, dkv_part 2 * N * H * hd floats when
+// attn_bwd_kv_partials(B, max_len, H, G); pos_ids (device int32 [N]) = each row's index inside
+// its sequence, the position of the fused inverse RoPE
+void attn_bwd_mfma_varlen(DType dt, const void* qkv, const void* o, const float* lse, const void* dout, void* dqkv,
+                          float* delta, float* dkv_part, const int* cu, const int* pos_ids, long N, int B, int max_len,
+                          int H, int G, int hd, const float* rcos, const float* rsin, hipStream_t s);
 
 // attn_f32.hip: fp32 flash attention on v_mfma_f32_32x32x2_f32 (head dims 64 / 128)
 bool attn_f32_head_dim(int hd);

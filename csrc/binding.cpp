@@ -401,6 +401,21 @@ void rope_dev_(Tensor& qkv, const Tensor& cos, const Tensor& sin, int64_t H, int
              (int)G, (int)hd, false, 0, stream(), pos.data_ptr<int>());
 }
 
+// RoPE of a packed variable-length batch: row r at position pos_ids[r] (int32 [N])
+void rope_pos_(Tensor& qkv, const Tensor& cos, const Tensor& sin, const Tensor& pos_ids, int64_t H, int64_t G,
+               int64_t hd, bool inverse) {
+  check_gpu(qkv, "qkv"); check_gpu(cos, "cos"); check_gpu(sin, "sin"); check_gpu(pos_ids, "pos_ids");
+  c10::DeviceGuard g(qkv.device());
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == (H + 2 * G) * hd && hd % 2 == 0 && qkv.is_contiguous(), "rope_pos_: qkv");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+              sin.is_contiguous() && cos.dim() == 2 && cos.size(1) == hd / 2 && sin.sizes() == cos.sizes(),
+              "rope_pos_: fp32 [ctx, hd/2] tables");
+  TORCH_CHECK(pos_ids.scalar_type() == at::kInt && pos_ids.is_contiguous() && pos_ids.numel() == qkv.size(0),
+              "rope_pos_: pos_ids must be int32 [N]");
+  bllm::rope_pos(dt_of(qkv), qkv.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), pos_ids.data_ptr<int>(),
+                 qkv.size(0), (int)H, (int)G, (int)hd, inverse, stream());
+}
+
 // ------------------------------------------------------------------ attention
 // db (+)= dy.sum(0): dy [N, F] bf16/fp16/fp32, db [F] any float dtype (written in place)
 void bias_grad_(const Tensor& dy, Tensor& db, bool accumulate) {
@@ -725,6 +740,56 @@ Tensor flash_attn_bwd(const Tensor& qkv, const Tensor& o, const Tensor& lse, con
                  delta.data_ptr<float>(), dkv_part.defined() ? dkv_part.data_ptr<float>() : nullptr, (int)B, (int)T, (int)H, (int)G, (int)hd, causal,
                  (float)p, (uint64_t)seed, (uint64_t)offset, keep_mask_ptr(keep_mask, qkv, B, T, H, hd, p),
                  rope_ptr(rope_cos, qkv, T, hd), rope_ptr(rope_sin, qkv, T, hd), stream());
+  return dqkv;
+}
+
+// Variable-length attention (causal, no dropout) on a packed batch: sequence b is rows
+// [cu[b], cu[b+1]) of qkv [N, (H+2G) hd]; bf16 / fp16, head dims 64 / 128 (the matrix-core kernels)
+static void check_varlen(const Tensor& qkv, const Tensor& cu, int64_t max_len, int64_t H, int64_t G, int64_t hd) {
+  check_gpu(qkv, "qkv"); check_gpu(cu, "cu");
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 || qkv.scalar_type() == at::kHalf, "flash_attn_varlen: bf16/fp16 only");
+  TORCH_CHECK(hd == 64 || hd == 128, "flash_attn_varlen: head_dim 64 or 128, got ", hd);
+  TORCH_CHECK(G > 0 && H % G == 0, "flash_attn_varlen: n_heads must be a multiple of n_kv_groups");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == (H + 2 * G) * hd && qkv.is_contiguous(), "flash_attn_varlen: qkv");
+  TORCH_CHECK(cu.scalar_type() == at::kInt && cu.is_contiguous() && cu.dim() == 1 && cu.numel() >= 1 &&
+              cu.device() == qkv.device(), "flash_attn_varlen: cu must be int32 [B + 1] on the qkv device");
+  TORCH_CHECK(max_len >= 0 && max_len <= qkv.size(0), "flash_attn_varlen: max_len");
+}
+
+std::tuple<Tensor, Tensor> flash_attn_varlen_fwd(const Tensor& qkv, const Tensor& cu, int64_t max_len, int64_t H,
+                                                 int64_t G, int64_t hd) {
+  check_varlen(qkv, cu, max_len, H, G, hd);
+  c10::DeviceGuard g(qkv.device());
+  const int64_t N = qkv.size(0), B = cu.numel() - 1;
+  auto o = at::empty({N, H * hd}, qkv.options());
+  auto lse = at::empty({H * N}, qkv.options().dtype(at::kFloat));
+  bllm::attn_fwd_mfma_varlen(dt_of(qkv), qkv.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), cu.data_ptr<int>(),
+                             (int)B, (int)max_len, (int)H, (int)G, (int)hd, stream());
+  return {o, lse};
+}
+
+Tensor flash_attn_varlen_bwd(const Tensor& qkv, const Tensor& o, const Tensor& lse, const Tensor& dout,
+                             const Tensor& cu, const Tensor& pos_ids, int64_t max_len, int64_t H, int64_t G,
+                             int64_t hd, const optional<Tensor>& rope_cos, const optional<Tensor>& rope_sin) {
+  check_varlen(qkv, cu, max_len, H, G, hd);
+  check_gpu(o, "o"); check_gpu(lse, "lse"); check_gpu(dout, "dout"); check_gpu(pos_ids, "pos_ids");
+  c10::DeviceGuard g(qkv.device());
+  const int64_t N = qkv.size(0), B = cu.numel() - 1;
+  TORCH_CHECK(o.scalar_type() == qkv.scalar_type() && dout.scalar_type() == qkv.scalar_type(), "flash_attn_varlen_bwd: dtypes");
+  TORCH_CHECK(o.is_contiguous() && dout.is_contiguous() && lse.is_contiguous(), "flash_attn_varlen_bwd: contiguous inputs");
+  TORCH_CHECK(o.sizes() == dout.sizes() && o.dim() == 2 && o.size(0) == N && o.size(1) == H * hd, "flash_attn_varlen_bwd: o / dout");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == H * N, "flash_attn_varlen_bwd: lse must be fp32 [H * N]");
+  TORCH_CHECK(pos_ids.scalar_type() == at::kInt && pos_ids.is_contiguous() && pos_ids.numel() == N,
+              "flash_attn_varlen_bwd: pos_ids must be int32 [N]");
+  auto dqkv = at::empty_like(qkv);
+  auto delta = at::empty({H * N}, qkv.options().dtype(at::kFloat));
+  auto dkv_part = bllm::attn_bwd_kv_partials((int)B, (int)max_len, (int)H, (int)G)
+                      ? at::empty({2, N, H, hd}, qkv.options().dtype(at::kFloat)) : Tensor();
+  bllm::attn_bwd_mfma_varlen(dt_of(qkv), qkv.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), dout.data_ptr(),
+                             dqkv.data_ptr(), delta.data_ptr<float>(),
+                             dkv_part.defined() ? dkv_part.data_ptr<float>() : nullptr, cu.data_ptr<int>(),
+                             pos_ids.data_ptr<int>(), N, (int)B, (int)max_len, (int)H, (int)G, (int)hd,
+                             rope_ptr(rope_cos, qkv, max_len, hd), rope_ptr(rope_sin, qkv, max_len, hd), stream());
   return dqkv;
 }
 
@@ -1176,6 +1241,9 @@ TORCH_LIBRARY(bllm, m) {
   m.def("attn_decode(Tensor q, Tensor kcache, Tensor vcache, int L) -> Tensor");
   m.def("attn_decode_append(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor");
   m.def("rope_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, int H, int G, int hd, Tensor pos) -> ()");
+  m.def("rope_pos_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos_ids, int H, int G, int hd, bool inverse) -> ()");
+  m.def("flash_attn_varlen_fwd(Tensor qkv, Tensor cu, int max_len, int H, int G, int hd) -> (Tensor, Tensor)");
+  m.def("flash_attn_varlen_bwd(Tensor qkv, Tensor o, Tensor lse, Tensor dout, Tensor cu, Tensor pos_ids, int max_len, int H, int G, int hd, Tensor? rope_cos=None, Tensor? rope_sin=None) -> Tensor");
   m.def("flash_attn_fwd(Tensor qkv, int B, int T, int H, int G, int hd, bool causal, float p, int seed, int offset, Tensor(a!)? keep_mask=None) -> (Tensor, Tensor)");
   m.def("flash_attn_bwd(Tensor qkv, Tensor o, Tensor lse, Tensor dout, int B, int T, int H, int G, int hd, bool causal, float p, int seed, int offset, Tensor? keep_mask=None, Tensor? rope_cos=None, Tensor? rope_sin=None) -> Tensor");
   m.def("ce_fwd(Tensor logits, Tensor targets, int ignore_index) -> (Tensor, Tensor)");
@@ -1228,6 +1296,9 @@ TORCH_LIBRARY_IMPL(bllm, CUDA, m) {
   m.impl("gemm_nt_bias_gelu_", &gemm_nt_bias_gelu_);
   m.impl("bias_grad_", &bias_grad_);
   m.impl("flash_attn_bwd", &flash_attn_bwd);
+  m.impl("rope_pos_", &rope_pos_);
+  m.impl("flash_attn_varlen_fwd", &flash_attn_varlen_fwd);
+  m.impl("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
   m.impl("ce_fwd", &ce_fwd);
   m.impl("ce_bwd_", &ce_bwd_);
   m.impl("embedding_fwd", &embedding_fwd);

@@ -441,6 +441,65 @@ __global__ __launch_bounds__(256) void rope_scalar_k(T* __restrict__ qkv, const 
   }
 }
 
+// RoPE by position ids (packed variable-length batches): row r is rotated at pos_ids[r], its
+// index inside its sequence, instead of r % T.  Same thread layout as rope_k / rope_scalar_k.
+template <typename T>
+__global__ __launch_bounds__(256) void rope_pos_k(T* __restrict__ qkv, const float* __restrict__ cosT,
+                                                  const float* __restrict__ sinT, long N, int nh_rot, int row_stride,
+                                                  int hd, float sgn, const int* __restrict__ pos_ids) {
+  static_assert(sizeof(T) == 2, "16-bit element types (fp32 uses rope_pos_scalar_k)");
+  const int half = hd / 2;
+  const int cpb = half / 8;  // chunks of 8 pairs per head
+  const int per_row = nh_rot * cpb;
+  const int total = (int)(N * per_row);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int r = i / per_row;
+    const int rem = i - r * per_row;
+    const int h = rem / cpb, ch = rem - h * cpb;
+    const int pos = pos_ids[r];
+    BLLM_DASSERT(pos >= 0, DBG_ROPE_POS);
+    T* base = qkv + (long)r * row_stride + h * hd + ch * 8;
+    const float* cp = cosT + (long)pos * half + ch * 8;
+    const float* sp = sinT + (long)pos * half + ch * 8;
+    const Vec16<T> a = ld16(base), b = ld16(base + half);
+    const float4 c0 = *reinterpret_cast<const float4*>(cp), c1 = *reinterpret_cast<const float4*>(cp + 4);
+    const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
+    const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    Vec16<T> oa, ob;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float x1 = to_f(a.v[j]), x2 = to_f(b.v[j]), sj = sgn * sn[j];
+      oa.v[j] = from_f<T>(x1 * c[j] - x2 * sj);
+      ob.v[j] = from_f<T>(x2 * c[j] + x1 * sj);
+    }
+    st16(base, oa);
+    st16(base + half, ob);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rope_pos_scalar_k(T* __restrict__ qkv, const float* __restrict__ cosT,
+                                                         const float* __restrict__ sinT, long N, int nh_rot,
+                                                         int row_stride, int hd, float sgn,
+                                                         const int* __restrict__ pos_ids) {
+  const int half = hd / 2;
+  const long total = N * nh_rot * half;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int k = (int)(i % half);
+    const long t = i / half;
+    const int h = (int)(t % nh_rot);
+    const long r = t / nh_rot;
+    const int pos = pos_ids[r];
+    BLLM_DASSERT(pos >= 0, DBG_ROPE_POS);
+    T* base = qkv + r * row_stride + (long)h * hd;
+    const float c = cosT[(long)pos * half + k], s = sgn * sinT[(long)pos * half + k];
+    const float a = to_f(base[k]), b = to_f(base[half + k]);
+    base[k] = from_f<T>(a * c - b * s);
+    base[half + k] = from_f<T>(b * c + a * s);
+  }
+}
+
 // Bias gradient db[f] (+)= sum_n dy[n, f]: replaces the eager column reduction of the GPT-2
 // bias grads (reference nn.Linear bias).  Pass 1: workgroup (x = 256 threads x 8-column
 // vectors, y = a row band) writes fp32 partial sums; pass 2 sums the bands in a fixed order and
@@ -704,6 +763,28 @@ void rope(DType dt, void* qkv, const float* cosT, const float* sinT, long N, int
       long tot = N * nh * (hd / 2);
       hipLaunchKernelGGL(rope_scalar_k<T>, dim3(ew_grid(tot)), dim3(256), 0, s, (T*)qkv, cosT, sinT, N, T_, nh,
                          stride, hd, pos_offset, sgn, pos_dev);
+    }
+  });
+}
+
+void rope_pos(DType dt, void* qkv, const float* cosT, const float* sinT, const int* pos_ids, long N, int H, int G,
+              int hd, bool inverse, hipStream_t s) {
+  const int nh = H + G, stride = (H + 2 * G) * hd;
+  const float sgn = inverse ? -1.f : 1.f;
+  if (N == 0) return;
+  BLLM_DISPATCH(dt, T, {
+    if constexpr (sizeof(T) == 2) {
+      if ((hd / 2) % 8 == 0) {
+        long tot = N * nh * (hd / 16);
+        hipLaunchKernelGGL(rope_pos_k<T>, dim3(ew_grid(tot)), dim3(256), 0, s, (T*)qkv, cosT, sinT, N, nh, stride, hd,
+                           sgn, pos_ids);
+        return;
+      }
+    }
+    {
+      long tot = N * nh * (hd / 2);
+      hipLaunchKernelGGL(rope_pos_scalar_k<T>, dim3(ew_grid(tot)), dim3(256), 0, s, (T*)qkv, cosT, sinT, N, nh, stride,
+                         hd, sgn, pos_ids);
     }
   });
 }

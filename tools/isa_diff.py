@@ -14,6 +14,12 @@ kernel (so its symbol changes) but must leave its instruction stream, register c
 size as they were.  Kernels are emitted in source order, so the indices of two trees line up as
 long as that order is unchanged.
 
+A file that gained kernels differs as a text, so a differing file is compared a second time
+kernel by kernel: the text of each function of BASE_TREE (its instructions, kernel descriptor,
+resource comments and metadata entry, with the per-file numbering of local labels dropped) must
+appear unchanged in NEW_TREE.  Such a file is reported as ``kernels identical (+N new)`` and
+does not count as a difference; a base kernel that is missing or altered does.
+
 Usage:
     python tools/isa_diff.py BASE_TREE [NEW_TREE] [--work DIR] [-j N] [--rename-symbols]
                              [--only release|debug] [--files a.hip b.hip ...]
@@ -69,6 +75,57 @@ def _normalise(path: str, rename: bool) -> list[str]:
     return text.split("\n")
 
 
+# per-file numbering of local labels, in label definitions, operands and loop comments
+_LOCAL = re.compile(r"(\.L|\b)(BB|func_end|func_begin|JTI|tmp)\d+")
+
+
+def _kernels(lines: list[str]) -> dict[str, list[str]]:
+    """Function name -> its text: the ``Begin function`` block (up to the next one or the
+    file's trailer) and its ``amdhsa.kernels`` metadata entry, local label numbers dropped."""
+    out: dict[str, list[str]] = {}
+    cur = None
+    meta: list[str] | None = None
+    in_meta = False
+
+    def close_meta():
+        nonlocal meta
+        if meta:
+            name = next((ln.split(":", 1)[1].strip() for ln in meta if ln.lstrip().startswith(".name:")), None)
+            if name:
+                out.setdefault(name, []).extend(meta)
+        meta = None
+
+    for ln in lines:
+        if in_meta:
+            if ln.startswith("  - "):
+                close_meta()
+                meta = [ln]
+            elif ln.startswith("    ") and meta is not None:
+                meta.append(ln)
+            else:
+                close_meta()
+                if ".end_amdgpu_metadata" in ln:
+                    in_meta = False
+            continue
+        if ".amdgpu_metadata" in ln:
+            in_meta, cur = True, None
+            continue
+        m = re.search(r"; -- Begin function (\S+)", ln)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif ln.startswith("\t.section\t.AMDGPU.gpr_maximums"):
+            cur = None
+        if cur is not None and not ln.startswith("\t.section\t.text."):
+            cur.append(_LOCAL.sub(lambda k: k.group(1) + k.group(2), ln))
+    return out
+
+
+def _per_kernel(x: list[str], y: list[str]) -> tuple[int, int]:
+    """(base kernels missing or altered in new, kernels only in new)"""
+    kx, ky = _kernels(x), _kernels(y)
+    return sum(1 for k, v in kx.items() if ky.get(k) != v), sum(1 for k in ky if k not in kx)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("base")
@@ -104,6 +161,10 @@ def main() -> int:
             if x == y:
                 row += f"{'identical (%d lines)' % len(x):>28s}"
             else:
+                changed, added = (1, 0) if a.rename_symbols else _per_kernel(x, y)
+                if changed == 0 and added > 0:
+                    row += f"{'kernels identical (+%d new)' % added:>28s}"
+                    continue
                 bad += 1
                 n = sum(1 for p, q in zip(x, y) if p != q) + abs(len(x) - len(y))
                 row += f"{'DIFFERS (%d lines)' % n:>28s}"
