@@ -29,6 +29,8 @@ def perform_checks(args):
         warnings.filterwarnings("ignore")
     if getattr(args, "unpad", False) and not (args.finetune and str(args.model).lower().startswith("llama")):
         raise ValueError("--unpad needs --finetune and a Llama model (GPT-2 is not supported).")
+    if getattr(args, "grad_accum_steps", 1) < 1:
+        raise ValueError("--grad_accum_steps must be at least 1.")
     if not os.path.exists(args.data_dir):
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -137,6 +139,10 @@ def build_parser() -> argparse.ArgumentParser:
     x.add_argument("--unpad", action="store_true",
                    help="instruction finetuning (Llama): run only each record's real rows, not the positions "
                         "the collate padded to the longest record (same loss and gradients)")
+    x.add_argument("--grad_accum_steps", type=int, default=1,
+                   help="loader batches (micro-batches of --batch_size rows) per optimizer step: the step one "
+                        "batch of all their rows would take (token-weighted); steps, --max_steps, the LR "
+                        "schedule and every *_freq count optimizer steps")
     x.add_argument("--no_plot", action="store_true")
     x.add_argument("--skip_final_save", action="store_true",
                    help="do not write model_pg_final.pth (throughput runs of multi-GB models)")
@@ -249,7 +255,10 @@ def main(rank: int, args):
                       max_steps=args.max_steps, sample_tokens=args.sample_tokens,
                       save_resume=args.save_resume_state, world_size=world, profile_steps=args.profile_steps,
                       num_workers=args.num_workers, seed=args.seed, comm_adapt_steps=args.comm_adapt_steps,
-                      unpad=args.unpad)
+                      unpad=args.unpad, grad_accum_steps=args.grad_accum_steps)
+    if rank == 0 and args.grad_accum_steps > 1:
+        logger.info(f"Gradient accumulation: {args.batch_size} rows x {args.grad_accum_steps} micro-batches x "
+                    f"{world} rank(s) = {args.batch_size * args.grad_accum_steps * world} rows per optimizer step")
     trainer.generate_and_print_sample("Every effort moves you", temperature=1.0, top_k=5, memory_check=True)
     if args.resume:
         # after the start-up sample: the restored host RNG state is the one saved at the checkpoint

@@ -64,6 +64,13 @@ class LocalEngine:
     def finish_backward(self):
         pass
 
+    def begin_micro_step(self, i: int, k: int):
+        """Micro-step ``i`` of ``k`` of one optimizer step is about to run its forward and backward
+        (train/accum.py).  From micro-step 1 on every gradient-writing kernel adds into the flat
+        gradients; engines with collectives also decide here whether this micro-step issues them.
+        ``begin_micro_step(0, 1)`` is the plain one-batch step."""
+        self.model.rctx.accumulate = i > 0
+
     @torch.no_grad()
     def load_full_state_dict(self, sd, strict: bool = True):
         return self.model.load_state_dict(sd, strict=strict)
@@ -344,6 +351,7 @@ class BaseLM(nn.Module):
         assert mode in ("none", "selective", "full"), mode
         self.use_actv_ckpt = mode != "none"
         object.__setattr__(self, "_rctx", RunCtx(cfg, mode))
+        self._rctx.engine = LocalEngine(self)
         object.__setattr__(self, "_comps", None)
         object.__setattr__(self, "_anchor", None)
 

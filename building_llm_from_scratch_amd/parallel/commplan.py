@@ -40,8 +40,10 @@ def _op(op, phase, numel, dtype, what, world):
             "what": what, "world": world}
 
 
-def step_plan(engine) -> List[Dict]:
-    """Ordered collectives of one steady-state training step (forward, backward, clip, step)."""
+def step_plan(engine, grad_accum_steps: int = 1) -> List[Dict]:
+    """Ordered collectives of one steady-state training step (forward, backward, clip, step).
+    With ``grad_accum_steps`` K > 1 the step runs K forwards and backwards: DDP and ZeRO-1 reduce
+    only in the last one (same plan); sharded FSDP gathers and reduce-scatters in every one."""
     from .ddp import DDPEngine
     from .fsdp import FSDPEngine
     from .zero import ZeroEngine
@@ -52,21 +54,22 @@ def step_plan(engine) -> List[Dict]:
             return plan
         units = engine.units
         last = len(units) - 1
-        # forward: one all-gather per buffer of every unit (units 0..prefetch_after_step-1 are
-        # issued right after their optimizer update of the previous step: same bytes)
-        for u in units:
-            for fb in u.state["bufs"]:
-                plan.append(_op("all_gather", "forward", fb.numel, fb.dtype, u.name, W))
-        # backward (reverse): re-gather every unit resharded after forward (all but the head),
-        # then reduce-scatter its gradient; the recompute of a checkpointed block reuses the
-        # gather its backward already holds
-        for u in reversed(units):
-            if engine.reshard_after_forward and u.index != last:
+        for _ in range(max(1, int(grad_accum_steps))):
+            # forward: one all-gather per buffer of every unit (units 0..prefetch_after_step-1 are
+            # issued right after their optimizer update of the previous step: same bytes)
+            for u in units:
                 for fb in u.state["bufs"]:
-                    plan.append(_op("all_gather", "backward", fb.numel, fb.dtype, u.name, W))
-            if u.train is not None:
-                rd = engine.reduce_dtype or u.train.grad.dtype
-                plan.append(_op("reduce_scatter", "backward", u.train.numel, rd, u.name, W))
+                    plan.append(_op("all_gather", "forward", fb.numel, fb.dtype, u.name, W))
+            # backward (reverse): re-gather every unit resharded after forward (all but the head),
+            # then reduce-scatter its gradient; the recompute of a checkpointed block reuses the
+            # gather its backward already holds
+            for u in reversed(units):
+                if engine.reshard_after_forward and u.index != last:
+                    for fb in u.state["bufs"]:
+                        plan.append(_op("all_gather", "backward", fb.numel, fb.dtype, u.name, W))
+                if u.train is not None:
+                    rd = engine.reduce_dtype or u.train.grad.dtype
+                    plan.append(_op("reduce_scatter", "backward", u.train.numel, rd, u.name, W))
         plan.append(_op("all_reduce", "clip", 1, torch.float32, "grad_sq_norm", W))
         return plan
     if isinstance(engine, (DDPEngine, ZeroEngine)):

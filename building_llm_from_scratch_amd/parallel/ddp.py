@@ -79,6 +79,11 @@ class DDPEngine(LocalEngine):
         self.bucket_mb = group_mb
 
     # ------------------------------------------------------------------ hooks
+    def begin_micro_step(self, i: int, k: int):
+        # gradients add up in the arena; only the last micro-step's backward all-reduces them
+        self.model.rctx.accumulate = i > 0
+        self.sync_grads = i == k - 1
+
     def pre_backward(self, unit):
         if not self._started:
             self._started = True

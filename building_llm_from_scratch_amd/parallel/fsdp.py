@@ -117,6 +117,7 @@ class FSDPEngine(LocalEngine):
         self.units = model.units
         self._rs_works: List = []
         self._in_backward = False
+        self._micro = 0               # micro-step of the optimizer step (begin_micro_step)
         model.set_engine(self)
 
     @staticmethod
@@ -224,6 +225,15 @@ class FSDPEngine(LocalEngine):
         return rec
 
     # ------------------------------------------------------------------ hooks
+    def begin_micro_step(self, i: int, k: int):
+        """Unsharded (``grad_shard is grad``): the kernels add in place from micro-step 1 on.
+        Sharded: a unit's full gradient lives only from its ``pre_backward`` to the retire of its
+        reduce-scatter, so every micro-step writes it afresh (accumulate off) and reduce-scatters
+        it; the retire writes the gradient shard in micro-step 0 and adds into it afterwards.
+        Holding full gradients across micro-steps would undo the sharding."""
+        self._micro = i
+        self.model.rctx.accumulate = self.no_shard and i > 0
+
     def pre_forward(self, unit):
         if self.prefetch_auto and unit.index == 0 and self._prefetch_tokens is None:
             self._size_prefetch()
@@ -258,18 +268,20 @@ class FSDPEngine(LocalEngine):
     def post_backward(self, unit):
         fb = unit.train
         if fb is not None and not self.no_shard:
-            if self.reduce_dtype is not None:
+            if self.reduce_dtype is not None or self._micro > 0:
                 # reduce in the policy's dtype: cast the full gradient, reduce-scatter into a
-                # reduce-dtype shard, cast back into the (param-dtype) gradient shard on retire
-                full = fb.grad.to(self.reduce_dtype)
-                part = torch.empty(fb.grad_shard.numel(), dtype=self.reduce_dtype, device=full.device)
+                # reduce-dtype shard, cast back into the (param-dtype) gradient shard on retire.
+                # Micro-steps after the first take the same route in any dtype: their shard is
+                # added to the gradient shard on retire, so it cannot be scattered into it
+                full = fb.grad.to(self.reduce_dtype) if self.reduce_dtype is not None else fb.grad
+                part = torch.empty(fb.grad_shard.numel(), dtype=full.dtype, device=full.device)
                 w = dist.reduce_scatter_tensor(part, full, group=self.pg, async_op=True)
                 self.comm.issued("reduce_scatter", w, full.numel() * full.element_size())
-                self._rs_works.append((w, fb, full, part))
+                self._rs_works.append((w, fb, full, part, self._micro > 0))
             else:
                 w = dist.reduce_scatter_tensor(fb.grad_shard, fb.grad, group=self.pg, async_op=True)
                 self.comm.issued("reduce_scatter", w, fb.grad.numel() * fb.grad.element_size())
-                self._rs_works.append((w, fb, None, None))
+                self._rs_works.append((w, fb, None, None, False))
             # the full gradient is released only after the reduce-scatter completed: freeing it
             # now would hand the block back to the compute stream's allocator pool while RCCL
             # may still be reading it (288 GB leaves room to hold them until the end of backward)
@@ -280,11 +292,13 @@ class FSDPEngine(LocalEngine):
         """Wait for and free all but the ``keep`` most recent reduce-scatters (bounded memory
         without stalling the stream on the one just issued)."""
         while len(self._rs_works) > keep:
-            w, fb, full, part = self._rs_works.pop(0)
+            w, fb, full, part, add = self._rs_works.pop(0)
             with self.comm.waiting("reduce_scatter"):
                 w.wait()
             self.comm.completed(w)
-            if part is not None:
+            if add:
+                fb.grad_shard.add_(part.to(fb.grad_shard.dtype))
+            elif part is not None:
                 fb.grad_shard.copy_(part)
             _free(fb.grad)
 

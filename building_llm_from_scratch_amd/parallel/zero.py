@@ -53,6 +53,7 @@ class ZeroEngine(LocalEngine):
             n = self.arena.bucket_grad(b).numel() // self.world_size
             self.grad_shards.append(torch.zeros(n, dtype=dtype, device=device))
         self.grad_prescale = 1.0 / self.world_size
+        self.sync_grads = True
         self._pending = []
         self._works = []
         self._started = False
@@ -62,6 +63,12 @@ class ZeroEngine(LocalEngine):
     def _shard(self, t: torch.Tensor) -> torch.Tensor:
         n = t.numel() // self.world_size
         return t[self.rank * n:(self.rank + 1) * n]
+
+    def begin_micro_step(self, i: int, k: int):
+        # gradients add up in the arena buckets; only the last micro-step's backward
+        # reduce-scatters them into the shards the optimizer reads
+        self.model.rctx.accumulate = i > 0
+        self.sync_grads = i == k - 1
 
     def pre_backward(self, unit):
         if not self._started:
@@ -78,7 +85,7 @@ class ZeroEngine(LocalEngine):
             self._launch(b)
 
     def _launch(self, b):
-        if self.no_comm:
+        if self.no_comm or not self.sync_grads:
             return
         g = self.arena.bucket_grad(b)
         if self.reduce_dtype is not None:

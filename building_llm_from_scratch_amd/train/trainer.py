@@ -12,7 +12,9 @@ log line format; returned (train_losses, val_losses, tokens_seen, lrs).
 Changed on purpose: exceptions propagate (no log-and-continue), ``calc_loss_loader``
 stops after ``num_batches`` (defect 8), logged losses / tokens are all-reduced across ranks
 (defect 12), plus a tokens/s metric, JSONL metrics, fp16 dynamic loss scaling, a non-finite
-loss guard, optional ``max_steps`` and resume state.
+loss guard, optional ``max_steps`` and resume state, and gradient accumulation
+(``grad_accum_steps``: one optimizer step per K loader batches, train/accum.py; every step count
+here -- ``global_step``, the schedule, the ``*_freq`` cadences -- is in optimizer steps).
 """
 from __future__ import annotations
 
@@ -81,8 +83,13 @@ class Trainer:
                  loss_scaler: Optional[DynamicLossScaler] = None, max_steps: Optional[int] = None,
                  sample_tokens: int = 200, save_resume: bool = False, world_size: int = 1,
                  profile_steps: Optional[str] = None, num_workers: int = 0, seed: int = 123,
-                 comm_adapt_steps: int = 3, unpad: bool = False):
+                 comm_adapt_steps: int = 3, unpad: bool = False, grad_accum_steps: int = 1):
         self.config = config
+        # loader batches (micro-batches) per optimizer step (train/accum.py); global_step, the LR
+        # schedule and every *_freq count optimizer steps
+        self.grad_accum_steps = int(grad_accum_steps)
+        if self.grad_accum_steps < 1:
+            raise ValueError("grad_accum_steps must be >= 1")
         # instruction finetuning on a Llama model: run only each row's real positions (those up to
         # its last non-ignored target) -- same loss and gradients, none of the padding's work
         self.unpad = bool(unpad)
@@ -216,10 +223,18 @@ class Trainer:
             self._seq = CollectiveSequence(timeout_s=self._seq_timeout_s)
         return self._seq
 
-    def _step_body(self, input_batch, target_batch):
-        loss = self.calc_loss_batch(input_batch, target_batch)
+    def _step_body(self, input_batch, target_batch, micro_batches=None):
+        if micro_batches is not None:
+            # K forwards and backwards into the same flat gradients; the overflow test, the clip
+            # and the optimizer step below run once, on the accumulated gradients
+            from .accum import accumulate_step
+            scale = self.loss_scaler.scale if self.loss_scaler is not None else None
+            loss = accumulate_step(self.model, micro_batches, loss_scale=scale, unpad=self.unpad)
+        else:
+            loss = self.calc_loss_batch(input_batch, target_batch)
         if self.loss_scaler is not None:
-            (loss * self.loss_scaler.scale).backward()
+            if micro_batches is None:
+                (loss * self.loss_scaler.scale).backward()
             inv = torch.tensor([1.0 / self.loss_scaler.scale], device=self.device)
             norm = self.optimizer.clip_grad_norm_(self.max_grad_norm, extra_scale=inv)
             overflow = not bool(torch.isfinite(norm).item())
@@ -228,12 +243,17 @@ class Trainer:
             elif self.rank == 0:
                 logger.warning(f"fp16 overflow at step {self.global_step}; loss scale -> {self.loss_scaler.scale}")
         else:
-            loss.backward()
+            if micro_batches is None:
+                loss.backward()
             self.optimizer.clip_grad_norm_(self.max_grad_norm)
             self.optimizer.step()
         return loss
 
-    def train_batch(self, input_batch, target_batch):
+    def train_group(self, micro_batches):
+        """One optimizer step over a list of (input, target) micro-batches (gradient accumulation)."""
+        return self.train_batch(None, None, micro_batches=list(micro_batches))
+
+    def train_batch(self, input_batch, target_batch, micro_batches=None):
         self.optimizer.zero_grad()
         self.global_step += 1
         adapting = (self.engine is not None and hasattr(self.engine, "adapt")
@@ -257,16 +277,17 @@ class Trainer:
         # raises naming the first differing call instead of hanging until the PG timeout
         seq = self._order_check()
         with seq.recording(f"step{self.global_step}") if seq is not None else contextlib.nullcontext():
-            loss = self._step_body(input_batch, target_batch)
+            loss = self._step_body(input_batch, target_batch, micro_batches)
         if seq is not None:
             seq.verify(f"step{self.global_step}")
         # this rank's own count (reference train.py:123 counts per rank); padded instruction
         # batches differ in length across ranks, so the node total is an exact sum
         # (_flush_tokens) at every eval / checkpoint point, never numel x world_size
-        if self.count_target_tokens:
-            self._tokens_pending += int((target_batch != IGNORE_INDEX).sum())
-        else:
-            self._tokens_pending += input_batch.numel()
+        for inp, tgt in (micro_batches if micro_batches is not None else [(input_batch, target_batch)]):
+            if self.count_target_tokens:
+                self._tokens_pending += int((tgt != IGNORE_INDEX).sum())
+            else:
+                self._tokens_pending += inp.numel()
         if adapting:
             self._sync()
             rec = self.engine.adapt(1e3 * (time.perf_counter() - t_step))
@@ -314,16 +335,29 @@ class Trainer:
         if skip_batches:
             it = itertools.islice(it, skip_batches, None)
         bi = skip_batches - 1
+        K = self.grad_accum_steps
         while True:
             t_wait = time.perf_counter()
-            try:
-                input_batch, target_batch = next(it)
-            except StopIteration:
-                break
+            if K == 1:
+                try:
+                    input_batch, target_batch = next(it)
+                except StopIteration:
+                    break
+                group = None
+                bi += 1
+            else:
+                # up to K loader batches per optimizer step; a group never spans data files, so
+                # a file's last group is stepped with the micro-batches it has
+                group = list(itertools.islice(it, K))
+                if not group:
+                    break
+                bi += len(group)
             self._data_wait += time.perf_counter() - t_wait   # host time blocked on the loader
-            bi += 1
             self.pos = (epoch_no, file_index, bi + 1)
-            loss = self.train_batch(input_batch, target_batch)
+            if group is None:
+                loss = self.train_batch(input_batch, target_batch)
+            else:
+                loss = self.train_group(group)
             if self.global_step % self.eval_freq == 0:
                 lv = float(loss.item())
                 # training throughput since the last eval point, measured up to this loss read
@@ -373,7 +407,12 @@ class Trainer:
 
     def _setup_schedule(self, n_epochs):
         self.peak_lr = self.optimizer.param_groups[0]["lr"]
-        self.total_training_steps = max(1, self.loaderObj.get_total_steps_epoch(self.data_files) * n_epochs)
+        if self.grad_accum_steps == 1:
+            per_epoch = self.loaderObj.get_total_steps_epoch(self.data_files)
+        else:   # optimizer steps: groups do not span files, each file's last one may be short
+            K = self.grad_accum_steps
+            per_epoch = sum(-(-self.loaderObj.get_total_steps_epoch([fp]) // K) for fp in self.data_files)
+        self.total_training_steps = max(1, per_epoch * n_epochs)
         if self.max_steps is not None:
             self.total_training_steps = min(self.total_training_steps, self.max_steps)
         self.lr_increment = (self.peak_lr - self.initial_lr) / max(1, self.warmup_steps)
@@ -481,12 +520,18 @@ class Trainer:
         st = {k: getattr(self, k) for k in self._STATE_KEYS}
         rc = self.model.rctx
         st.update(pos=list(self.pos), rng_seed=int(rc.seed), rng_offset=int(rc._offset),
-                  data_order_version=self.DATA_ORDER_VERSION,
+                  data_order_version=self.DATA_ORDER_VERSION, grad_accum_steps=self.grad_accum_steps,
                   loss_scale=(self.loss_scaler.scale if self.loss_scaler else None),
                   loss_scale_clean=(self.loss_scaler.clean if self.loss_scaler else None))
         return st
 
     def load_trainer_state(self, st: dict):
+        # the saved data position counts loader batches: under another K it would fall inside a
+        # group of micro-batches (states written before gradient accumulation existed are K = 1)
+        saved_k = int(st.get("grad_accum_steps", 1))
+        if saved_k != self.grad_accum_steps:
+            raise ValueError(f"resume state was written with --grad_accum_steps {saved_k}; this run uses "
+                             f"{self.grad_accum_steps}. Resume with the same value.")
         for k in self._STATE_KEYS:
             setattr(self, k, st[k])
         if "pos" in st:

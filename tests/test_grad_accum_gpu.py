@@ -1,0 +1,234 @@
+"""Gradient accumulation on the GPU (train/accum.py): the ``accumulate=True`` branch of every
+gradient-writing kernel inside a real step.  Each GPU model steps over K micro-batches and is
+compared with the CPU fp32 model on the one batch made of their rows, at the bounds of
+tests/test_unpad_gpu.py::_check_model (bf16: loss 2e-2, per-parameter relative-norm gradient error
+5e-2; fp32: 1e-4 and 1e-3)."""
+import functools
+import json
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+from numerics import close_ratio
+
+from building_llm_from_scratch_amd import ops
+from building_llm_from_scratch_amd.config import get_config
+from building_llm_from_scratch_amd.data.datasets import custom_collate_fn
+from building_llm_from_scratch_amd.models import build_model, replace_linear_with_lora
+from building_llm_from_scratch_amd.models.llama import MIN_CHUNK_ROWS
+from building_llm_from_scratch_amd.train.accum import accumulate_step
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+DEV = "cuda"
+
+
+@pytest.fixture(autouse=True)
+def _ext():
+    assert ops.load_ext(required=True)
+    torch.manual_seed(0)
+
+
+def _cfgs():
+    # tests/test_model_gpu.py::_cfgs
+    llama = get_config("llama3_1", "8B").replace(context_length=256, emb_dim=512, n_heads=8, n_kv_groups=2,
+                                                 hidden_dim=768, n_layers=2, vocab_size=1000)
+    llama128 = get_config("llama3", "8B").replace(context_length=256, emb_dim=512, n_heads=4, n_kv_groups=1,
+                                                  hidden_dim=512, n_layers=2, vocab_size=1000)
+    gpt = get_config("GPT2", "124M").replace(context_length=256, emb_dim=256, n_heads=4, n_kv_groups=4,
+                                             hidden_dim=1024, n_layers=2, vocab_size=1000, drop_rate=0.0)
+    return {"llama_hd64": llama, "llama_hd128": llama128, "gpt2": gpt}
+
+
+def _rel(a, b):
+    a, b = a.float().cpu(), b.float().cpu()
+    return ((a - b).norm() / (b.norm() + 1e-12)).item()
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(name, rows):
+    """The CPU fp32 model on ONE [rows, 256] batch: its state, the batch, loss and gradients.
+    Computed once per (model, rows) and shared (checkpoint modes and dtypes do not change it)."""
+    cfg = _cfgs()[name]
+    torch.manual_seed(0)
+    m = build_model(cfg.replace(dtype=torch.float32))
+    g = torch.Generator().manual_seed(11)
+    idx = torch.randint(0, cfg.vocab_size, (rows, 257), generator=g)
+    loss = m(idx[:, :-1], idx[:, 1:])
+    loss.backward()
+    return {"sd": {k: v.detach().clone() for k, v in m.state_dict().items()}, "idx": idx, "loss": loss.item(),
+            "grads": {k: p.grad.detach().clone() for k, p in m.named_parameters()}}
+
+
+def _gpu_model(name, dt, ckpt, sd):
+    m = build_model(_cfgs()[name].replace(dtype=dt), use_actv_ckpt=ckpt, device=DEV)
+    m.load_state_dict(sd)
+    return m
+
+
+def _micro(idx, rows):
+    return [(idx[r:r + rows, :-1], idx[r:r + rows, 1:]) for r in range(0, idx.shape[0], rows)]
+
+
+def _check(m, loss, ref, dt, what=""):
+    tol = 2e-2 if dt == torch.bfloat16 else 1e-4
+    gtol = 5e-2 if dt == torch.bfloat16 else 1e-3
+    errs = {k: _rel(p.grad, ref["grads"][k]) for k, p in m.named_parameters() if p.requires_grad}
+    worst = max(errs, key=errs.get)
+    print(f"{what}: loss {loss.item():.6f} (oracle {ref['loss']:.6f}), worst gradient {errs[worst]:.3e} ({worst})")
+    assert abs(loss.item() - ref["loss"]) < tol * abs(ref["loss"]), (loss.item(), ref["loss"])
+    assert errs and set(errs) == set(ref["grads"])
+    for k, e in errs.items():
+        assert e < gtol, (k, e)
+    assert m.rctx.accumulate is False
+
+
+# ------------------------------------------------------------------ 1. Llama, 2. GPT-2
+@pytest.mark.parametrize("name", ["llama_hd64", "llama_hd128"])
+@pytest.mark.parametrize("ckpt", ["none", "selective", "full"])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
+def test_llama_three_micro_batches(name, ckpt, dt):
+    """Three micro-batches of [1, 256] (256 rows: the dW kernel's smallest K): one first write and
+    two accumulates into every flat gradient."""
+    ref = _oracle(name, 3)
+    m = _gpu_model(name, dt, ckpt, ref["sd"])
+    loss = accumulate_step(m, _micro(ref["idx"], 1))
+    _check(m, loss, ref, dt, f"{name} {ckpt} {dt}")
+
+
+def test_gpt2_three_micro_batches():
+    """LayerNorm dW / dB, ``wpe`` and the bias sums riding in the dropout and GELU backward passes."""
+    ref = _oracle("gpt2", 3)
+    m = _gpu_model("gpt2", torch.bfloat16, "none", ref["sd"])
+    loss = accumulate_step(m, _micro(ref["idx"], 1))
+    _check(m, loss, ref, torch.bfloat16, "gpt2")
+
+
+# ------------------------------------------------------------------ 3. split-K dW under accumulation
+def test_split_k_wgrad_accumulates(monkeypatch):
+    """Two micro-batches of [8, 256]: at 2,048 rows ``ops.wgrad_plan`` splits K two ways for every
+    projection of this model, so micro-step 1 runs the partial sum followed by accumulate."""
+    ref = _oracle("llama_hd64", 16)
+    m = _gpu_model("llama_hd64", torch.bfloat16, "none", ref["sd"])
+    calls, orig = [], ops.wgrad_gemm_
+
+    def spy(a, b, c, accumulate=False, splits=None):
+        calls.append((bool(accumulate), ops.wgrad_plan(a.shape[1], b.shape[1], a.shape[0])))
+        return orig(a, b, c, accumulate, splits)
+
+    monkeypatch.setattr(ops, "wgrad_gemm_", spy)
+    loss = accumulate_step(m, _micro(ref["idx"], 8))
+    print("dW calls (accumulate, plan):", sorted(set(calls)))
+    acc = [plan for a, plan in calls if a]
+    # micro-step 1 adds into the flat gradient of every block projection (qkv, out, gate/up, down);
+    # the fused head's dW is always taken into its own buffer first and never accumulates here
+    assert len(acc) == 4 * m.cfg.n_layers, len(acc)
+    assert all(plan == ("split", 2) for plan in acc), sorted(set(acc))
+    _check(m, loss, ref, torch.bfloat16, "split-K")
+
+
+# ------------------------------------------------------------------ 4. LoRA, K-augmented, unpadded
+def test_lora_kaug_unpadded_micro_batches():
+    """The set-up of test_unpad_gpu.py::test_unpadded_gpu_lora_model_kaug_path: two ragged
+    micro-batches of 2 rows, each packed on its own, against the padded CPU batch."""
+    cfg = _cfgs()["llama_hd64"]
+    ms = []
+    for dt, dev in ((torch.float32, None), (torch.bfloat16, DEV)):
+        torch.manual_seed(0)
+        m = build_model(cfg.replace(dtype=dt), device=dev) if dev else build_model(cfg.replace(dtype=dt))
+        for p in m.parameters():
+            p.requires_grad = False
+        replace_linear_with_lora(m, rank=16, alpha=32)
+        for mod in m.modules():
+            if hasattr(mod, "B") and isinstance(mod.B, torch.nn.Parameter):
+                torch.nn.init.normal_(mod.B, std=0.05)
+        m.flatten()
+        ms.append(m)
+    ref_m, gpu_m = ms
+    gpu_m.load_state_dict(ref_m.state_dict())
+    blk = gpu_m.computes[1]
+    assert blk.qkv.kaug_input(torch.zeros(MIN_CHUNK_ROWS, cfg.emb_dim, device=DEV, dtype=torch.bfloat16),
+                              cfg.emb_dim) is not None
+    g = torch.Generator().manual_seed(11)
+    recs = [(3, torch.randint(0, 999, (n,), generator=g).tolist()) for n in (40, 255, 7, 130)]
+    x, y = custom_collate_fn(recs, pad_token_id=999)
+    lr = ref_m(x, y)
+    lr.backward()
+    ref = {"loss": lr.item(), "grads": {k: p.grad for k, p in ref_m.named_parameters() if p.requires_grad}}
+    loss = accumulate_step(gpu_m, [(x[:2], y[:2]), (x[2:], y[2:])], unpad=True)
+    assert gpu_m.rctx.seq is not None and gpu_m.rctx.seq.N % MIN_CHUNK_ROWS == 0
+    _check(gpu_m, loss, ref, torch.bfloat16, "lora kaug unpad")
+
+
+# ------------------------------------------------------------------ 5. engines
+def _helper(mode, timeout):
+    r = subprocess.run([sys.executable, os.path.join(HERE, "_grad_accum_engines.py"), mode, "fsdp,zero1,ddp"],
+                       capture_output=True, text=True, timeout=timeout, env={**os.environ, "BLLM_FORCE_COMM": "0"})
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    res = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    print(mode, json.dumps(res))
+    return res
+
+
+def test_engines_k2_forced_comm_on_rccl():
+    """Bounds of test_engines_gpu.py::test_engines_forced_comm_match_local_on_rccl."""
+    res = _helper("rccl", 300)
+    for kind in ("fsdp", "zero1", "ddp"):
+        k = res[kind]
+        assert k["keys_match"]
+        assert k["no_shard"] is False or k["no_comm"] is False, k   # the collective path ran
+        assert k["losses"] == pytest.approx(res["ref_losses"], abs=1e-3), (kind, k["losses"], res["ref_losses"])
+        assert k["max_param_diff"] < 1e-2, (kind, k["max_param_diff"])
+
+
+def test_engines_k2_world2_gloo_on_one_gpu():
+    """Bounds of test_engines_gpu.py::test_engines_world2_gloo_on_one_gpu."""
+    res = _helper("gloo2", 420)
+    for kind in ("fsdp", "zero1", "ddp"):
+        k = res[kind]
+        assert k["keys_match"], kind
+        assert k["losses"] == pytest.approx(res["ref_losses"], rel=2e-2), (kind, k["losses"], res["ref_losses"])
+        assert k["max_rel_diff"] < 5e-2, (kind, k["max_rel_diff"])
+
+
+# ------------------------------------------------------------------ 6. determinism
+def test_accumulated_step_is_bitwise_deterministic():
+    ref = _oracle("llama_hd64", 3)
+    grads = []
+    for _ in range(2):
+        m = _gpu_model("llama_hd64", torch.bfloat16, "selective", ref["sd"])
+        accumulate_step(m, _micro(ref["idx"], 1))
+        grads.append({k: p.grad.detach().clone() for k, p in m.named_parameters()})
+    for k in grads[0]:
+        assert torch.equal(grads[0][k], grads[1][k]), k
+
+
+# ------------------------------------------------------------------ 7. bf16 accumulation error
+def test_bf16_accumulation_error_recorded():
+    """K = 8 micro-batches of one row against the single 8-row bf16 batch, both measured against
+    the fp32 one-batch oracle with ``numerics.close_ratio`` (worst per parameter class).  Asserted:
+    the project bound only.  Measured on an MI355X (profiles/r8/grad_accum/): close_ratio 2.6-6.4
+    accumulated against 2.2-6.5 for the one batch, relative norm 4.4e-3 - 9.5e-3 against
+    3.4e-3 - 9.0e-3."""
+    ref = _oracle("llama_hd64", 8)
+    bf16 = torch.bfloat16
+    m_acc = _gpu_model("llama_hd64", bf16, "none", ref["sd"])
+    loss = accumulate_step(m_acc, _micro(ref["idx"], 1))
+    m_one = _gpu_model("llama_hd64", bf16, "none", ref["sd"])
+    m_one(ref["idx"][:, :-1], ref["idx"][:, 1:]).backward()
+    one = dict(m_one.named_parameters())
+    table = {}
+    for k, p in m_acc.named_parameters():
+        cls = re.sub(r"^(trf_blocks|blocks)\.\d+\.", "", k)
+        a = close_ratio(p.grad, ref["grads"][k], bf16)
+        b = close_ratio(one[k].grad, ref["grads"][k], bf16)
+        row = table.setdefault(cls, [0.0, 0.0, 0.0, 0.0])
+        row[0], row[1] = max(row[0], a), max(row[1], b)
+        row[2], row[3] = max(row[2], _rel(p.grad, ref["grads"][k])), max(row[3], _rel(one[k].grad, ref["grads"][k]))
+    print("class | close_ratio K=8 | close_ratio one batch | rel-norm K=8 | rel-norm one batch")
+    for cls, (a, b, ra, rb) in table.items():
+        print(f"{cls} | {a:.3f} | {b:.3f} | {ra:.3e} | {rb:.3e}")
+    _check(m_acc, loss, ref, bf16, "K=8")
