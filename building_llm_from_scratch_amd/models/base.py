@@ -4,8 +4,8 @@ The reference runs every model as a plain ``nn.Module`` forward under autograd (
 node per eager op, ``[B,H,T,T]`` scores materialised; reference GPT2.py:108-124,
 Llama3.py:196-204).  Here a model is an ordered list of *units* (embedding -> blocks ->
 final norm + head) and each unit is ONE autograd node whose forward/backward is written by
-hand (models/gpt2.py, models/llama.py) on top of the HIP kernels and hipBLASLt GEMMs.  That
-gives exact control over:
+hand (models/gpt2.py, models/llama.py, models/head.py) on top of the HIP kernels and hipBLASLt
+GEMMs.  That gives exact control over:
 
   * what each block saves for backward (``actv_ckpt``: ``none`` | ``selective`` — recompute
     only the norm outputs and the SwiGLU / GELU activation, the cheapest memory-bound ops (the
@@ -24,6 +24,7 @@ gives exact control over:
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from contextlib import contextmanager
 from typing import List, Optional
 
@@ -268,6 +269,11 @@ class _EmbedFn(torch.autograd.Function):
         return None, None, None
 
 
+# what a fully checkpointed block keeps instead of its saved state: its input and the forward's
+# replay token (GPT-2's dropout offsets)
+_Recompute = namedtuple("_Recompute", "x replay")
+
+
 class _BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, comp):
@@ -277,7 +283,7 @@ class _BlockFn(torch.autograd.Function):
         y, saved = comp.forward(x, save=not full)
         eng.post_forward(comp.unit)
         ctx.comp = comp
-        ctx.saved = ("__recompute__", x, saved) if full else saved
+        ctx.saved = _Recompute(x, saved) if full else saved
         return y
 
     @staticmethod
@@ -286,10 +292,8 @@ class _BlockFn(torch.autograd.Function):
         eng = comp.rctx.engine
         eng.pre_backward(comp.unit)
         saved = ctx.saved
-        if isinstance(saved, tuple) and len(saved) == 3 and isinstance(saved[0], str) \
-                and saved[0] == "__recompute__":
-            _, x, replay = saved
-            _, saved = comp.forward(x, save=True, replay=replay, recompute=True)
+        if isinstance(saved, _Recompute):
+            _, saved = comp.forward(saved.x, save=True, replay=saved.replay, recompute=True)
         dx = comp.backward(dy.contiguous(), saved)
         ctx.saved = None
         eng.post_backward(comp.unit)

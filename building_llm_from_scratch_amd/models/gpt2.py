@@ -12,7 +12,8 @@ regenerate them instead of storing them; GPU kernels and the CPU path produce id
 
 Execution per block: LayerNorm[HIP] -> QKV GEMM (+bias epilogue) -> flash attention with
 in-kernel dropout[HIP MFMA] -> out-proj GEMM (+bias) -> dropout+residual[HIP] -> LayerNorm
--> fc GEMM (+bias) -> GELU[HIP] -> proj GEMM (+bias) -> dropout+residual[HIP].
+-> fc GEMM (+bias) -> GELU[HIP] -> proj GEMM (+bias) -> dropout+residual[HIP].  The final
+LayerNorm's unit runs the head and the loss of models/head.py.
 """
 from __future__ import annotations
 
@@ -22,8 +23,8 @@ import torch.nn as nn
 
 from .. import ops
 from .base import BaseLM, UnitCompute, cached_attention
+from .head import HeadComputeMixin
 from .linear import FusedLinear
-from .llama import HeadComputeMixin
 
 
 class MultiHeadAttention(nn.Module):
@@ -293,10 +294,6 @@ class GPTHeadCompute(HeadComputeMixin, UnitCompute):
 
     def layout(self):
         return [[self.m.norm.weight, self.m.norm.bias]] + self.head.layout()
-
-    def bind(self, unit):
-        super().bind(unit)
-        self.head.bind(unit)
 
     def _norm_fwd(self, x2d):
         u, n = self.unit, self.m.norm

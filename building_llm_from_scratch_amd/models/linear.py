@@ -20,9 +20,13 @@ a fixed number of launches per group however many members it has.  Two forms:
            dA_m = s x^T u_m (lora_wgrad, into the flat gradient), dx += s u P (lora_up)
 Groups the kernels cannot take (fp32, ranks not a multiple of 16, odd widths) use per-member
 hipBLASLt GEMMs.
+
+What a forward hands its backward is typed: :class:`KaugCtx`, :class:`GroupedCtx`, or the
+per-member list of ``x A``; a backward told ``lowrank_dx`` returns a :class:`LowRankDx`.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -206,10 +210,53 @@ def use_gemm_epilogues(on=True) -> None:
     FUSED_SWIGLU, FUSED_ROPE, FUSED_GELU = "swiglu" in names, "rope" in names, "gelu" in names
 
 
+class KaugCtx(namedtuple("KaugCtx", "st P WaT")):
+    """Saved by a K-augmented forward: st = s t (the augmented columns, a view into [x | s t | 0]),
+    P = A_cat^T [R, K], WaT = [W^T ; Bd]."""
+
+    def compact(self) -> "KaugCtx":
+        """The s t columns copied out of their buffer (whose x part the caller drops)."""
+        return self._replace(st=self.st.contiguous())
+
+
+# saved by a grouped forward: t = x A_cat [N, R], P = A_cat^T [R, K]
+GroupedCtx = namedtuple("GroupedCtx", "t P")
+# dx = base + scale * u P, left for the consumer to form (the arguments of ops.swiglu_bwd_lowrank after gu)
+LowRankDx = namedtuple("LowRankDx", "base u P scale")
+
+
+class FrozenDerived:
+    """Something built from a frozen weight, rebuilt only when the weight's storage or version
+    changed (a re-gather, a state-dict load)."""
+    key = value = None
+
+    def get(self, W: torch.Tensor, build):
+        key = (W.data_ptr(), W._version, W.shape, W.dtype)
+        if self.key != key:
+            self.key, self.value = key, build(W)
+        return self.value
+
+
+def zero_buffer(buf: Optional[torch.Tensor], rows: int, cols: int, like: torch.Tensor) -> torch.Tensor:
+    """``buf`` while it is a [rows, cols] buffer of ``like``'s dtype and device, else a new zeroed
+    one: kept across steps by callers that rewrite the live part and rely on the rest being zero."""
+    if buf is None or buf.shape != (rows, cols) or buf.dtype != like.dtype or buf.device != like.device:
+        return torch.zeros(rows, cols, dtype=like.dtype, device=like.device)
+    return buf
+
+
+def _lora_wgrad(a: torch.Tensor, b: torch.Tensor, targets, scale: float, accumulate: bool):
+    """ops.lora_wgrad into ``targets`` = [(grad view, its column of a, its column of b)]."""
+    if targets:
+        ops.lora_wgrad(a, b, *(list(t) for t in zip(*targets)), scale, accumulate)
+
+
 class FusedLinear:
     def __init__(self, modules: Sequence[nn.Module]):
         self.modules = list(modules)
         self.specs: List[LinearSpec] = []
+        self._wa = FrozenDerived()       # ([W | Bd^T], [W^T ; Bd]) of a K-augmented group (``_waug``)
+        self.wt_copy = FrozenDerived()   # K-contiguous W^T, for a caller's own dX GEMMs (models/head.py)
 
     def refresh(self):
         self.specs = [resolve(m) for m in self.modules]
@@ -282,19 +329,16 @@ class FusedLinear:
         K-contiguous operand).  Kept across calls: the frozen W parts are re-copied only when
         W's storage or version changed (a re-gather, a state-dict load); the B blocks (trained)
         are rewritten every call, one kernel each."""
-        u = self.unit
         Rp = self._kaug_pad(K)
-        key = (W.data_ptr(), W._version, W.shape, W.dtype)
-        cached = getattr(self, "_wa_cache", None)
-        if cached is not None and cached[0] == key:
-            Wa, WaT = cached[1], cached[2]
-        else:
+
+        def build(W):
             Wa = torch.empty(W.shape[0], K + Rp, dtype=W.dtype, device=W.device)
             Wa[:, :K].copy_(W)
             WaT = torch.empty(K + Rp, W.shape[0], dtype=W.dtype, device=W.device)
             WaT[:K].copy_(ops.transpose2d(W) if W.is_cuda else W.t())
-            self._wa_cache = (key, Wa, WaT)
-        Bs = [u.data(s.lora_B) for s in self.lora_specs]
+            return Wa, WaT
+        Wa, WaT = self._wa.get(W, build)
+        Bs = [self.unit.data(s.lora_B) for s in self.lora_specs]
         ops.lora_block_(Wa[:, K:], Bs, self.lora_c0, self.lora_off)
         ops.lora_block_(WaT[K:].t(), Bs, self.lora_c0, self.lora_off)
         return Wa, WaT
@@ -311,7 +355,7 @@ class FusedLinear:
         ops.lora_down_into(x, [P], [0], [K], [0], R, self.lora_scale, xa[:, K:])  # [s x A_cat | 0]
         Wa, WaT = self._waug(self.W(), K)
         y = ops.linear_residual(xa, Wa, residual) if residual is not None else mm_nt(xa, Wa)
-        return y, ("kaug", xa[:, K:K + R], P, WaT)
+        return y, KaugCtx(xa[:, K:K + R], P, WaT)
 
     # views are re-fetched every call: FSDP may have re-materialised the storage
     def W(self):
@@ -343,7 +387,7 @@ class FusedLinear:
             ops.lora_up_(y, t, [u.data(s.lora_B) for s in self.lora_specs], self.lora_c0,
                          self.lora_off, self.lora_scale, base=residual, bias=b)
             y.addmm_(x, W.t())
-            return y, ("grouped", t, P)
+            return y, GroupedCtx(t, P)
         if residual is not None:
             y = ops.linear_residual(x, W, residual)
         elif b is not None:
@@ -406,7 +450,7 @@ class FusedLinear:
         u = self.unit
         if self._grouped_lora(x):
             P = ops.lora_pack_t([u.data(s.lora_A) for s in self.lora_specs])
-            return ("grouped", ops.lora_down(x, [P], [0], [x.shape[1]], [0], self.lora_R), P)
+            return GroupedCtx(ops.lora_down(x, [P], [0], [x.shape[1]], [0], self.lora_R), P)
         return [torch.mm(x, u.data(s.lora_A)) if s.lora_A is not None else None for s in self.specs]
 
     # ------------------------------------------------------------------ bwd
@@ -417,13 +461,15 @@ class FusedLinear:
 
     def backward(self, dy: torch.Tensor, x: torch.Tensor, xa, need_dx: bool = True,
                  accumulate: bool = False, dx_acc: Optional[torch.Tensor] = None, bias_done: bool = False,
-                 lowrank_dx: bool = False, defer_lora_A: bool = False, lora_B_done: bool = False):
+                 lowrank_dx: bool = False, lora_A_done: bool = False, lora_B_done: bool = False):
         """Returns dx (plus ``dx_acc`` if given) and writes parameter grads into the flat.
-        ``lowrank_dx``: a K-augmented group may instead return ("lowrank", base, u, P, s, A_deferred)
-        with dx = base + s u P left for the consumer to form (ops.swiglu_bwd_lowrank); with
-        ``defer_lora_A`` that consumer also sums dA = s x^T u (A_deferred True: ops.swiglu_bwd_lowrank_wgrad).
-        ``lora_B_done``: the caller already summed the K-augmented group's dB (same kernel)."""
+        ``lowrank_dx`` (only where ``lowrank_dx_ok``): return a :class:`LowRankDx` instead, dx =
+        base + s u P left for the consumer to form (ops.swiglu_bwd_lowrank).  ``lora_A_done`` /
+        ``lora_B_done`` (K-augmented groups only): the caller's own kernel sums that factor's
+        gradients (ops.swiglu_bwd_lowrank_wgrad), so this call leaves them alone."""
         u = self.unit
+        assert not lowrank_dx or (need_dx and dx_acc is None and self.lowrank_dx_ok(xa, x.shape[1]))
+        assert not (lora_A_done or lora_B_done) or isinstance(xa, KaugCtx)
         gW = u.fused_grad(self.W_params)
         if gW is not None:
             _weight_grad(dy, x, gW, accumulate)
@@ -431,11 +477,11 @@ class FusedLinear:
             gb = u.fused_grad(self.b_params)
             if gb is not None:
                 ops.bias_grad_(dy, gb, accumulate)
-        if self.has_lora and isinstance(xa, tuple) and xa[0] == "kaug":
-            return self._kaug_lora_backward(dy, x, xa[1], xa[2], xa[3], need_dx, dx_acc, accumulate, lowrank_dx,
-                                            defer_lora_A, lora_B_done)
-        if self.has_lora and isinstance(xa, tuple) and xa[0] == "grouped":
-            return self._grouped_lora_backward(dy, x, xa[1], xa[2], need_dx, dx_acc, accumulate)
+        if isinstance(xa, KaugCtx):
+            return self._kaug_lora_backward(dy, x, xa, need_dx, dx_acc, accumulate, lowrank_dx, lora_A_done,
+                                            lora_B_done)
+        if isinstance(xa, GroupedCtx):
+            return self._grouped_lora_backward(dy, x, xa, need_dx, dx_acc, accumulate)
         dx = None
         if need_dx:
             dx = _input_grad(dy, self.W(), dx_acc)
@@ -469,52 +515,49 @@ class FusedLinear:
         assert not self.has_lora
         return _input_grad(dy, self.W())
 
-    def _kaug_lora_backward(self, dy, x, st, P, WaT, need_dx, dx_acc, accumulate, lowrank_dx=False,
-                            defer_A=False, B_done=False):
-        """st = s t (the forward's augmented columns), WaT = [W^T ; Bd]."""
-        u_ = self.unit
+    def lowrank_dx_ok(self, xa, K: int) -> bool:
+        """Whether ``backward(..., lowrank_dx=True)`` can hand this saved context's dX (input
+        width K) back as a :class:`LowRankDx`."""
+        return isinstance(xa, KaugCtx) and ops.swiglu_bwd_lowrank_ok(self.lora_R, K)
+
+    def _lora_grad_targets(self):
+        """([(gB_m, its column of t, its column of dy)], [(gA_m^T, its column of u, 0)]) of the
+        group's trainable members: the target lists of the two ``_lora_wgrad`` passes."""
+        u = self.unit
+        gB = [(u.grad(s.lora_B), off, c0) for s, c0, off in zip(self.lora_specs, self.lora_c0, self.lora_off)]
+        gA = [(u.grad(s.lora_A), off, 0) for s, off in zip(self.lora_specs, self.lora_off)]
+        return [g for g in gB if g[0] is not None], [(g.t(), off, c) for g, off, c in gA if g is not None]
+
+    def _kaug_lora_backward(self, dy, x, ctx: KaugCtx, need_dx, dx_acc, accumulate, lowrank_dx, A_done, B_done):
         sc = self.lora_scale
         K = x.shape[1]
-        gB = [(u_.grad(s.lora_B), c0, off) for s, c0, off in zip(self.lora_specs, self.lora_c0, self.lora_off)]
-        gB = [g for g in gB if g[0] is not None]
-        if gB and not B_done:                                      # dB = s t^T dy = (s t)^T dy
-            ops.lora_wgrad(st, dy, [g for g, _, _ in gB], [o for _, _, o in gB], [c for _, c, _ in gB], 1.0,
-                           accumulate)
-        dxa = mm_nt(dy, WaT)                                       # [dy W | dy Bd | 0] = [dx_W | dy B^T | 0]
+        gB, gA = self._lora_grad_targets()
+        if not B_done:
+            _lora_wgrad(ctx.st, dy, gB, 1.0, accumulate)              # dB = s t^T dy = (s t)^T dy
+        dxa = mm_nt(dy, ctx.WaT)                                      # [dy W | dy Bd | 0] = [dx_W | dy B^T | 0]
         ub = dxa[:, K:K + self.lora_R]
-        lowrank = need_dx and lowrank_dx and dx_acc is None and ops.swiglu_bwd_lowrank_ok(self.lora_R, K)
-        defer = lowrank and defer_A
-        gA = [(u_.grad(s.lora_A), off) for s, off in zip(self.lora_specs, self.lora_off)]
-        gA = [g for g in gA if g[0] is not None]
-        if gA and not defer:
-            ops.lora_wgrad(ub, x, [g.t() for g, _ in gA], [o for _, o in gA], [0] * len(gA), sc, accumulate)
+        if not A_done:
+            _lora_wgrad(ub, x, gA, sc, accumulate)                    # dA = s x^T (dy B^T)
         if not need_dx:
             return None
-        if lowrank:
-            return ("lowrank", dxa[:, :K], ub, P, sc, defer)      # the consumer adds s u P (and dA)
+        if lowrank_dx:
+            return LowRankDx(dxa[:, :K], ub, ctx.P, sc)               # the consumer adds s u P
         dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        ops.lora_up_(dx, ub, [P], [0], [0], sc, base=dxa[:, :K])  # dx_W + s (dy B^T) A_cat^T
+        ops.lora_up_(dx, ub, [ctx.P], [0], [0], sc, base=dxa[:, :K])  # dx_W + s (dy B^T) A_cat^T
         if dx_acc is not None:
             dx += dx_acc
         return dx
 
-    def _grouped_lora_backward(self, dy, x, t, P, need_dx, dx_acc, accumulate):
-        u_ = self.unit
+    def _grouped_lora_backward(self, dy, x, ctx: GroupedCtx, need_dx, dx_acc, accumulate):
         sc = self.lora_scale
-        Bs = [u_.data(s.lora_B) for s in self.lora_specs]
+        Bs = [self.unit.data(s.lora_B) for s in self.lora_specs]
         u = ops.lora_down(dy, Bs, self.lora_c0, self.lora_len, self.lora_off, self.lora_R)   # dy B^T
-        gB = [(u_.grad(s.lora_B), c0, off) for s, c0, off in zip(self.lora_specs, self.lora_c0, self.lora_off)]
-        gB = [g for g in gB if g[0] is not None]
-        if gB:
-            ops.lora_wgrad(t, dy, [g for g, _, _ in gB], [o for _, _, o in gB], [c for _, c, _ in gB], sc,
-                           accumulate)
-        gA = [(u_.grad(s.lora_A), off) for s, off in zip(self.lora_specs, self.lora_off)]
-        gA = [g for g in gA if g[0] is not None]
-        if gA:
-            ops.lora_wgrad(u, x, [g.t() for g, _ in gA], [o for _, o in gA], [0] * len(gA), sc, accumulate)
+        gB, gA = self._lora_grad_targets()
+        _lora_wgrad(ctx.t, dy, gB, sc, accumulate)
+        _lora_wgrad(u, x, gA, sc, accumulate)
         if not need_dx:
             return None
         # dx = dx_acc + s u A_cat^T (lora_up, write-only) then += dy W (beta = 1 GEMM)
         dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        ops.lora_up_(dx, u, [P], [0], [0], sc, base=dx_acc)
+        ops.lora_up_(dx, u, [ctx.P], [0], [0], sc, base=dx_acc)
         return _input_grad(dy, self.W(), out=dx)

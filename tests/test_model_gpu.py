@@ -195,7 +195,7 @@ def test_fp16_fused_head_under_loss_scaling(name, monkeypatch):
     tails p / nvalid below fp16's subnormal range are not flushed before scaling.  Its gradients
     must match the unfused head (full fp16 logits, CE backward at dloss = scale) and the fp32
     CPU oracle."""
-    from building_llm_from_scratch_amd.models import llama as L
+    from building_llm_from_scratch_amd.models import head as L
     ops.load_ext(required=True)
     cfg = _cfgs()[name].replace(vocab_size=32000)
     S = 65536.0

@@ -20,6 +20,24 @@ def _small_gpt2(**kw):
                        n_layers=2, vocab_size=97, dtype=torch.float32, drop_rate=0.0, **kw)
 
 
+def _count_ops(monkeypatch, *names):
+    """Count the model's calls of ``ops.<name>`` -> {name: calls so far}.  A call that one counted
+    op makes from inside another (the CPU path of a fused op built on a simpler one) is the op's
+    business, not the model's, and is not counted."""
+    counts = dict.fromkeys(names, 0)
+    depth = [0]
+    for n in names:
+        def spy(*a, _n=n, _f=getattr(ops, n), **k):
+            counts[_n] += depth[0] == 0
+            depth[0] += 1
+            try:
+                return _f(*a, **k)
+            finally:
+                depth[0] -= 1
+        monkeypatch.setattr(ops, n, spy)
+    return counts
+
+
 def _compare(model, loss_fn, idx, tgt, atol=2e-5):
     loss = model(idx, tgt)
     loss.backward()
@@ -151,9 +169,9 @@ def test_fused_chunked_lora_head(family, monkeypatch):
     """LoRA head (frozen base) on the chunked head + CE with the rank-r path folded into the
     head GEMMs ([h | s t] . [W | B^T]^T): several chunks, ignore_index targets, non-unit dloss,
     vs the eager oracle."""
-    from building_llm_from_scratch_amd.models import llama
-    monkeypatch.setattr(llama, "MIN_CHUNK_ROWS", 8)
-    monkeypatch.setattr(llama, "LOGIT_CHUNK_BYTES", 8 * 97 * 4)
+    from building_llm_from_scratch_amd.models import head as head_mod
+    monkeypatch.setattr(head_mod, "MIN_CHUNK_ROWS", 8)
+    monkeypatch.setattr(head_mod, "LOGIT_CHUNK_BYTES", 8 * 97 * 4)
     torch.manual_seed(0)
     cfg = _small_llama() if family == "llama" else _small_gpt2()
     m = build_model(cfg)
@@ -174,6 +192,9 @@ def test_fused_chunked_lora_head(family, monkeypatch):
         fn = lambda sd: llama_loss(sd, cfg, idx, tgt, cos, sin, lora=2.0)  # noqa: E731
     else:
         fn = lambda sd: gpt2_loss(sd, cfg, idx, tgt, lora=2.0)  # noqa: E731
+    counts = _count_ops(monkeypatch, "ce_fwd")
+    m(idx, tgt)
+    assert counts["ce_fwd"] > 1, counts          # the patched chunk sizes are the ones the head reads
     _compare(m, fn, idx, tgt)
     (m(idx, tgt) * 4.0).backward()
     g4 = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
@@ -188,9 +209,9 @@ def test_fused_chunked_head_ce(family, monkeypatch):
     """Head + CE fused chunk by chunk (logits never materialised whole): several chunks, a
     chunk boundary inside the sequence, ignore_index targets, and a non-unit dloss (fp16 loss
     scaling path) all give the eager-autograd gradients."""
-    from building_llm_from_scratch_amd.models import llama
-    monkeypatch.setattr(llama, "MIN_CHUNK_ROWS", 8)
-    monkeypatch.setattr(llama, "LOGIT_CHUNK_BYTES", 8 * 97 * 4)   # 8 rows of fp32 logits per chunk
+    from building_llm_from_scratch_amd.models import head as head_mod
+    monkeypatch.setattr(head_mod, "MIN_CHUNK_ROWS", 8)
+    monkeypatch.setattr(head_mod, "LOGIT_CHUNK_BYTES", 8 * 97 * 4)   # 8 rows of fp32 logits per chunk
     torch.manual_seed(0)
     cfg = _small_llama() if family == "llama" else _small_gpt2()
     m = build_model(cfg)
@@ -202,6 +223,9 @@ def test_fused_chunked_head_ce(family, monkeypatch):
         fn = lambda sd: llama_loss(sd, cfg, idx, tgt, cos, sin)  # noqa: E731
     else:
         fn = lambda sd: gpt2_loss(sd, cfg, idx, tgt)  # noqa: E731
+    counts = _count_ops(monkeypatch, "ce_fwd")
+    m(idx, tgt)
+    assert counts["ce_fwd"] == 5, counts         # 39 rows in chunks of 8: the patched sizes are read
     _compare(m, fn, idx, tgt)
     # dloss != 1: gradients scale exactly (unit backwards overwrite the flat gradients)
     (m(idx, tgt) * 4.0).backward()
@@ -218,6 +242,86 @@ def test_fused_chunked_head_ce(family, monkeypatch):
     m.rctx.loss_scale = 1.0
     for n in g1:
         assert torch.allclose(gs[n], g1[n], rtol=1e-5, atol=1e-7), n
+
+
+@pytest.mark.parametrize("rank,wgrad_on,expect", [(16, True, (1, 0, 0)), (16, False, (0, 1, 0)), (4, True, (0, 0, 1))])
+def test_mlp_lora_fusion_truth_table(rank, wgrad_on, expect, monkeypatch):
+    """Which SwiGLU backward a LoRA MLP runs, per block: with K-augmented rank-16 groups the one
+    that forms the low-rank dX and sums the gate/up dB and down dA (LORA_SWIGLU_WGRAD), or the
+    one that only forms the low-rank dX; any other rank the plain one on a full d_act.  Exactly
+    one of the three per block, and the eager oracle's gradients on each."""
+    from building_llm_from_scratch_amd.models import linear, llama
+    monkeypatch.setattr(linear, "FORCE_GROUPED_LORA", True)
+    monkeypatch.setattr(llama, "LORA_SWIGLU_WGRAD", wgrad_on)
+    torch.manual_seed(0)
+    cfg = _small_llama().replace(hidden_dim=128)
+    m = build_model(cfg, use_actv_ckpt="none")
+    for p in m.parameters():
+        p.requires_grad = False
+    replace_linear_with_lora(m, rank=rank, alpha=8)
+    for mod in m.modules():
+        if hasattr(mod, "B") and isinstance(mod.B, torch.nn.Parameter):
+            torch.nn.init.normal_(mod.B, std=0.05)
+    m.flatten()
+    idx = torch.randint(0, cfg.vocab_size, (2, 16))
+    tgt = torch.randint(0, cfg.vocab_size, (2, 16))
+    cos, sin = ops.rope_tables(cfg.head_dim, cfg.context_length, cfg.rope_base, cfg.rope_freq)
+    names = ("swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank", "swiglu_bwd")
+    counts = _count_ops(monkeypatch, *names)
+    _compare(m, lambda sd: llama_loss(sd, cfg, idx, tgt, cos, sin, lora=8 / rank), idx, tgt)
+    assert tuple(counts[n] for n in names) == tuple(e * cfg.n_layers for e in expect), counts
+
+
+def test_block_saved_state_is_never_taken_for_the_recompute_marker():
+    """A block whose saved state is itself a 3-tuple that starts with a string goes to its
+    ``backward`` as it is: only _BlockFn's own marker type means "recompute the forward"."""
+    from building_llm_from_scratch_amd.models.base import LocalEngine, _BlockFn, _Recompute
+    state = ("__recompute__", torch.zeros(1), "replay")
+    seen = []
+
+    class Comp:
+        unit, index = None, 0
+
+        class rctx:
+            engine = LocalEngine()
+            mode = "none"
+
+            @classmethod
+            def block_mode(cls, i):
+                return cls.mode
+
+        def forward(self, x, save, replay=None, recompute=False):
+            seen.append(("forward", save, replay, recompute))
+            return x * 2.0, (state if save else "token")
+
+        def backward(self, dy, saved):
+            seen.append(("backward", saved))
+            return dy * 2.0
+
+    x = torch.ones(2, 3, requires_grad=True)
+    _BlockFn.apply(x, Comp()).sum().backward()
+    assert seen == [("forward", True, None, False), ("backward", state)]
+    assert torch.equal(x.grad, torch.full((2, 3), 2.0))
+    # and the marker itself: the forward is re-run on the kept input with the replay token
+    del seen[:]
+    Comp.rctx.mode = "full"
+    _BlockFn.apply(x, Comp()).sum().backward()
+    assert seen == [("forward", False, None, False), ("forward", True, "token", True), ("backward", state)]
+    assert not isinstance(state, _Recompute)
+
+
+def test_chunk_constants_cannot_be_patched_on_llama(monkeypatch):
+    """The head's chunk constants are models.head's.  Patching them on models.llama, where they
+    used to live, raises instead of setting a name nobody reads; MIN_CHUNK_ROWS can still be read
+    there and follows models.head."""
+    from building_llm_from_scratch_amd.models import head as head_mod, llama
+    with pytest.raises(AttributeError):
+        llama.MIN_CHUNK_ROWS = 8             # (what monkeypatch.setattr does after its getattr)
+    with pytest.raises(AttributeError):
+        monkeypatch.setattr(llama, "LOGIT_CHUNK_BYTES", 8)
+    assert not hasattr(llama, "LOGIT_CHUNK_BYTES")
+    monkeypatch.setattr(head_mod, "MIN_CHUNK_ROWS", 8)
+    assert llama.MIN_CHUNK_ROWS == 8
 
 
 def test_selective_rebuilds_activation_and_norms():

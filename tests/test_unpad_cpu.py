@@ -14,7 +14,7 @@ from building_llm_from_scratch_amd import cli
 from building_llm_from_scratch_amd.config import get_config
 from building_llm_from_scratch_amd.data.datasets import custom_collate_fn, unpad_lengths
 from building_llm_from_scratch_amd.models import build_model, replace_linear_with_lora
-from building_llm_from_scratch_amd.models.llama import MIN_CHUNK_ROWS
+from building_llm_from_scratch_amd.models.head import MIN_CHUNK_ROWS
 from building_llm_from_scratch_amd.ops import reference as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
