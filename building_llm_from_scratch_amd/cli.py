@@ -31,7 +31,15 @@ def perform_checks(args):
         raise ValueError("--unpad needs --finetune and a Llama model (GPT-2 is not supported).")
     if getattr(args, "grad_accum_steps", 1) < 1:
         raise ValueError("--grad_accum_steps must be at least 1.")
-    if not os.path.exists(args.data_dir):
+    gen_only = getattr(args, "generate_only", False)
+    if gen_only and not getattr(args, "generate_prompts", None):
+        raise ValueError("--generate_only needs --generate_prompts FILE.")
+    if getattr(args, "generate_prompts", None):
+        if not os.path.isfile(args.generate_prompts):
+            raise FileNotFoundError(f"--generate_prompts file '{args.generate_prompts}' does not exist.")
+        if getattr(args, "generate_max_tokens", 256) < 1:
+            raise ValueError("--generate_max_tokens must be at least 1.")
+    if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
         else:
@@ -143,6 +151,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="loader batches (micro-batches of --batch_size rows) per optimizer step: the step one "
                         "batch of all their rows would take (token-weighted); steps, --max_steps, the LR "
                         "schedule and every *_freq count optimizer steps")
+    x.add_argument("--generate_prompts", type=str, default=None,
+                   help="after training, answer the prompts of this JSON list in batches of --batch_size "
+                        "(train/generate.py:generate_ragged, greedy): an item is a string, used verbatim, or an "
+                        "Alpaca entry, prompted the way --finetune trains (its fields + '### Response:')")
+    x.add_argument("--generate_out", type=str, default=None,
+                   help="where rank 0 writes the [{prompt, response}] list (default <output_dir>/responses.json)")
+    x.add_argument("--generate_max_tokens", type=int, default=256, help="new tokens per prompt at most")
+    x.add_argument("--generate_only", action="store_true",
+                   help="no data preparation, training or final save: build the model (--load_weights / "
+                        "--resume), answer --generate_prompts, exit")
     x.add_argument("--no_plot", action="store_true")
     x.add_argument("--skip_final_save", action="store_true",
                    help="do not write model_pg_final.pth (throughput runs of multi-GB models)")
@@ -194,6 +212,45 @@ def _prepare_data(args, cfg, rank):
     return files
 
 
+def load_generate_prompts(path):
+    """``--generate_prompts`` file -> (items, prompt texts).  An item is a string, used verbatim, or
+    an Alpaca entry, which becomes ``format_input(entry) + "\\n\\n### Response:\\n"`` -- the prefix
+    ``InstructionDataset`` trains on."""
+    import json
+
+    from .data.datasets import format_input
+    with open(path, "r", encoding="utf-8") as f:
+        items = json.load(f)
+    if not isinstance(items, list) or not items:
+        raise ValueError(f"--generate_prompts: {path} must hold a non-empty JSON list")
+    texts = []
+    for i, it in enumerate(items):
+        if isinstance(it, str):
+            texts.append(it)
+        elif isinstance(it, dict) and "instruction" in it:
+            texts.append(format_input(it) + "\n\n### Response:\n")
+        else:
+            raise ValueError(f"--generate_prompts: item {i} is neither a string nor an entry with an 'instruction'")
+    return items, texts
+
+
+def _generate_responses(trainer, args, rank, out_dir):
+    """Answer ``--generate_prompts`` (all ranks: the engines gather parameters collectively);
+    rank 0 writes [{"prompt", "response"}] in input order, an entry's own fields kept."""
+    import json
+    items, texts = load_generate_prompts(args.generate_prompts)
+    responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size)
+    if rank != 0:
+        return
+    rows = [{**(it if isinstance(it, dict) else {}), "prompt": t, "response": r}
+            for it, t, r in zip(items, texts, responses)]
+    path = Path(args.generate_out) if args.generate_out else out_dir / "responses.json"
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(rows, f, indent=2, ensure_ascii=False)
+    logger.info(f"Wrote {len(rows)} responses to {path}")
+
+
 def main(rank: int, args):
     import torch.distributed as dist
 
@@ -219,15 +276,18 @@ def main(rank: int, args):
     utils.set_seed(args.seed)
     config, model, optimizer, tokenizer, engine = build_components(rank, device, args)
 
-    _prepare_data(args, config, rank)
-    if args.run_type == "multi_gpu":
-        dist.barrier()
-    all_files = sorted(os.path.join(path, n) for path, _, fs in os.walk(args.data_dir) for n in fs
-                       if n.endswith((".txt", ".json")))
-    if not all_files:
-        raise FileNotFoundError("No training files found in specified directory.")
-    if rank == 0:
-        logger.info(f"Total training files detected: {len(all_files)}")
+    gen_only = getattr(args, "generate_only", False)
+    all_files = []
+    if not gen_only:
+        _prepare_data(args, config, rank)
+        if args.run_type == "multi_gpu":
+            dist.barrier()
+        all_files = sorted(os.path.join(path, n) for path, _, fs in os.walk(args.data_dir) for n in fs
+                           if n.endswith((".txt", ".json")))
+        if not all_files:
+            raise FileNotFoundError("No training files found in specified directory.")
+        if rank == 0:
+            logger.info(f"Total training files detected: {len(all_files)}")
 
     kw = dict(tokenizer=tokenizer, batch_size=args.batch_size, max_length=config["context_length"],
               dataset_name=args.dataset, run_type=args.run_type, train_ratio=0.9)
@@ -239,7 +299,7 @@ def main(rank: int, args):
         loader = DataloaderPT(stride=config["context_length"], eos_text=config["eos_text"], collate_func=None,
                               cache_dir=cache, **kw)
         # rank 0 tokenises every file once into the memmapped cache; the others map it
-        if cache and rank == 0:
+        if cache and rank == 0 and all_files:
             loader.pretokenize(all_files)
         if cache and args.run_type == "multi_gpu":
             dist.barrier()
@@ -259,6 +319,12 @@ def main(rank: int, args):
     if rank == 0 and args.grad_accum_steps > 1:
         logger.info(f"Gradient accumulation: {args.batch_size} rows x {args.grad_accum_steps} micro-batches x "
                     f"{world} rank(s) = {args.batch_size * args.grad_accum_steps * world} rows per optimizer step")
+    if gen_only:
+        _generate_responses(trainer, args, rank, out_dir)
+        if args.run_type == "multi_gpu":
+            dist.barrier()
+            dist.destroy_process_group()
+        return trainer
     trainer.generate_and_print_sample("Every effort moves you", temperature=1.0, top_k=5, memory_check=True)
     if args.resume:
         # after the start-up sample: the restored host RNG state is the one saved at the checkpoint
@@ -283,6 +349,8 @@ def main(rank: int, args):
             logger.info(f"Maximum GPU memory used: {torch.cuda.max_memory_allocated() / 1e9:.2f} GB")
     if not args.skip_final_save:
         trainer.save_checkpoint("model_pg_final.pth")
+    if getattr(args, "generate_prompts", None):
+        _generate_responses(trainer, args, rank, out_dir)
     if args.run_type == "multi_gpu":
         dist.barrier()
         dist.destroy_process_group()

@@ -157,6 +157,19 @@ class SeqPack:
         self.pos_ids = pos.to(torch.int32).to(device, non_blocking=True)   # each row's index in its sequence
 
 
+def pack_prompts(prompts, device):
+    """Ragged inference batch: 1-D token tensors of any lengths -> (idx [N] on ``device``, SeqPack)
+    with sequence b = rows [bounds[b], bounds[b+1]).  No row-count rounding and no pad sequences
+    (``sel`` is None: there is no padded layout the rows were taken from)."""
+    lens = [int(p.numel()) for p in prompts]
+    bounds = [0]
+    for n in lens:
+        bounds.append(bounds[-1] + n)
+    pos = torch.cat([torch.arange(n) for n in lens])
+    idx = torch.cat([p.reshape(-1).to(torch.long) for p in prompts]).to(device, non_blocking=True)
+    return idx, SeqPack(None, pos, bounds, device)
+
+
 def pack_sequences(in_idx: torch.Tensor, targets: torch.Tensor, seq_lens, row_multiple: int, device,
                    ignore_index: int = -100):
     """Compact ``in_idx`` / ``targets`` [B, T] to rows (b, 0 .. seq_lens[b] - 1) in batch order ->
@@ -591,6 +604,42 @@ class BaseLM(nn.Module):
         x = comps[0].infer_dev(idx, pos_t)
         for c, kv in zip(comps[1:-1], cache):
             x = c.infer_dev(x, pos_t, kv)
+        return comps[-1].infer(x, idx.shape[0], 1)
+
+    # -- ragged batches: every row at its own position --------------------------------------
+    @torch.no_grad()
+    def forward_prefill_ragged(self, idx_packed: torch.Tensor, seq: SeqPack, cache) -> torch.Tensor:
+        """Prefill of a ragged batch: ``idx_packed`` [N] holds the prompts back to back, sequence b
+        at rows [seq.bounds[b], seq.bounds[b+1]) (``pack_prompts``).  One unpadded pass
+        (variable-length attention, positions from ``seq.pos_ids``) that fills rows 0 .. len_b - 1
+        of ``cache`` row b; returns the logits [B, V] after each sequence's last token.  Call inside
+        ``engine.params_resident()`` like :meth:`forward_cached`."""
+        self._ensure_flat()
+        comps, rc = self._comps, self._rctx
+        kc = cache[0][0]
+        nseq = len(seq.bounds) - 1
+        if nseq != kc.shape[0] or seq.max_len > kc.shape[2]:
+            raise ValueError(f"ragged prefill: {nseq} sequences of at most {seq.max_len} tokens do not fit a cache "
+                             f"of {kc.shape[0]} rows x {kc.shape[2]} positions")
+        if min(b - a for a, b in zip(seq.bounds[:-1], seq.bounds[1:])) < 1:
+            raise ValueError("ragged prefill: every sequence needs at least one token")
+        rc.sync_all_params()
+        idx = idx_packed.reshape(-1).to(self._anchor.device)
+        x = comps[0].infer_ragged(idx, seq)
+        for c, kv in zip(comps[1:-1], cache):
+            x = c.infer_ragged(x, seq, kv)
+        return comps[-1].infer_rows(x, (seq.cu[1:] - 1).to(torch.long))
+
+    @torch.no_grad()
+    def forward_cached_rows(self, idx: torch.Tensor, cache, pos_rows: torch.Tensor) -> torch.Tensor:
+        """:meth:`forward_cached_dev` with a position per row: one decode token per row (idx [B, 1]),
+        row b at ``pos_rows[b]`` (int32 [B] on the device, each below the cache length and the
+        model's context length -- the caller's entry check, train/generate.py:generate_ragged).
+        No host read, so the step can be captured in a HIP graph wherever :meth:`decode_graph_ok`."""
+        comps = self._comps
+        x = comps[0].infer_rows(idx, pos_rows)
+        for c, kv in zip(comps[1:-1], cache):
+            x = c.infer_rows(x, pos_rows, kv)
         return comps[-1].infer(x, idx.shape[0], 1)
 
     def sync_params(self):

@@ -94,6 +94,12 @@ class GPTEmbedCompute(UnitCompute):
         wpe = self.unit.data(self.m.pos_emb.weight)
         return wte.index_select(0, idx.reshape(-1)) + wpe.index_select(0, pos_t)
 
+    infer_rows = infer_dev          # pos_t of B elements: row b's learned position is wpe[pos_t[b]]
+
+    def infer_ragged(self, idx, seq):
+        """Packed prompt rows: row r's learned position is its index inside its sequence."""
+        return self.infer_dev(idx, seq.pos_ids)
+
     def backward(self, dx, saved):
         idx, p, off = saved
         rc = self.rctx
@@ -166,6 +172,31 @@ class GPTBlockCompute(UnitCompute):
         f, _ = self.fc.forward(self._ln(x2, b.norm2)[0])
         m, _ = self.proj.forward(ops.gelu_fwd(f))
         return x2 + m
+
+    def _infer_out(self, x2d, o):
+        """Everything after attention (inference: no dropout): out projection, residual, GELU MLP."""
+        b = self.block
+        a, _ = self.o.forward(o)
+        x2 = x2d + a
+        f, _ = self.fc.forward(self._ln(x2, b.norm2)[0])
+        m, _ = self.proj.forward(ops.gelu_fwd(f))
+        return x2 + m
+
+    def infer_rows(self, x2d, pos_rows, kv):
+        """``infer_dev`` with a position per row (int32 [B] on the device)."""
+        H = self.rctx.cfg.n_heads
+        qkv, _ = self.qkv.forward(self._ln(x2d, self.block.norm1)[0])
+        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, H))
+
+    def infer_ragged(self, x2d, seq, kv):
+        """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,
+        and the K / V of sequence b into rows 0 .. len_b - 1 of cache row b."""
+        cfg = self.rctx.cfg
+        H, hd = cfg.n_heads, cfg.head_dim
+        qkv, _ = self.qkv.forward(self._ln(x2d, self.block.norm1)[0])
+        o, _ = ops.flash_attn_varlen_fwd(qkv, seq.cu, seq.max_len, H, H, hd, bounds=seq.bounds)
+        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1])
+        return self._infer_out(x2d, o)
 
     def infer(self, x2d, B, t, pos, kv):
         cfg, b = self.rctx.cfg, self.block

@@ -57,6 +57,12 @@ class HeadComputeMixin:
         logits, _ = self.forward_logits(last, save=False)
         return logits
 
+    def infer_rows(self, x2d, rows):
+        """Logits of the packed rows ``rows`` (LongTensor on the device) only: a ragged prefill
+        needs the head on each sequence's last row, not on all N."""
+        logits, _ = self.forward_logits(x2d.index_select(0, rows), save=False)
+        return logits
+
     def forward_logits(self, x, save):
         x2d = x.reshape(-1, x.shape[-1])
         h, ns = self._norm_fwd(x2d)

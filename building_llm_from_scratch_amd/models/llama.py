@@ -137,6 +137,11 @@ class LlamaEmbedCompute(UnitCompute):
         W = self.unit.data(self.m.tok_emb.weight)
         return ops.embedding_fwd(idx.reshape(-1).contiguous(), W, None, 1)
 
+    infer_rows = infer_dev          # per-row positions: no learned positions to look up
+
+    def infer_ragged(self, idx, seq):
+        return self.infer_dev(idx, None)
+
 
 class LlamaBlockCompute(UnitCompute):
     def __init__(self, rctx, block: TransformerBlock, i: int):
@@ -261,6 +266,42 @@ class LlamaBlockCompute(UnitCompute):
         gu, _ = self.gu.forward(h2)
         x3, _ = self.down.forward(ops.swiglu_fwd(gu), residual=x2)
         return x3
+
+    def _infer_qkv(self, x2d):
+        u, b = self.unit, self.block
+        h1, _ = ops.rmsnorm_fwd(x2d, u.data(b.norm1.weight), self.rctx.cfg.norm_eps)
+        return self.qkv.forward(h1)[0]
+
+    def _infer_out(self, x2d, o):
+        """Everything after attention: out projection + residual, norm2, SwiGLU MLP + residual."""
+        u, b = self.unit, self.block
+        x2, _ = self.o.forward(o, residual=x2d)
+        h2, _ = ops.rmsnorm_fwd(x2, u.data(b.norm2.weight), self.rctx.cfg.norm_eps)
+        gu, _ = self.gu.forward(h2)
+        x3, _ = self.down.forward(ops.swiglu_fwd(gu), residual=x2)
+        return x3
+
+    def infer_rows(self, x2d, pos_rows, kv):
+        """``infer_dev`` with a position per row (int32 [B] on the device): RoPE rotates row b at
+        ``pos_rows[b]`` and the decode kernel appends and attends there."""
+        cfg = self.rctx.cfg
+        H, G, hd = cfg.n_heads, cfg.n_kv_groups, cfg.head_dim
+        cos, sin = self.rctx.rope
+        qkv = self._infer_qkv(x2d)
+        ops.rope_pos_(qkv, cos, sin, pos_rows, H, G, hd)
+        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G))
+
+    def infer_ragged(self, x2d, seq, kv):
+        """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,
+        and the rotated K / V of sequence b into rows 0 .. len_b - 1 of cache row b."""
+        cfg = self.rctx.cfg
+        H, G, hd = cfg.n_heads, cfg.n_kv_groups, cfg.head_dim
+        cos, sin = self.rctx.rope
+        qkv = self._infer_qkv(x2d)
+        ops.rope_pos_(qkv, cos, sin, seq.pos_ids, H, G, hd)
+        o, _ = ops.flash_attn_varlen_fwd(qkv, seq.cu, seq.max_len, H, G, hd, bounds=seq.bounds)
+        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1])
+        return self._infer_out(x2d, o)
 
     def infer(self, x2d, B, t, pos, kv):
         cfg, u, b = self.rctx.cfg, self.unit, self.block

@@ -26,7 +26,7 @@ __all__ = [
     "flash_attn_varlen_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
     "swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank_wgrad_ok",
     "gelu_fwd", "gelu_bwd", "gelu_bwd_bias", "gelu_bwd_act", "dropout_bwd_bias", "ce_fwd", "ce_bwd_", "embedding_fwd", "embedding_bwd",
-    "sq_norm_multi", "adamw_step_", "attn_decode", "bias_grad_", "ext_available", "load_ext", "attention_backend",
+    "sq_norm_multi", "adamw_step_", "attn_decode", "attn_decode_append_rows", "kv_cache_fill_varlen", "bias_grad_", "ext_available", "load_ext", "attention_backend",
     "lora_down", "lora_up_", "lora_wgrad", "lora_pack_t", "lora_kernel_ok", "lora_kernel_ok_dims",
     "lora_down_into", "lora_block_", "rmsnorm_fwd_into", "swiglu_fwd_into", "sum_partials_",
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
@@ -276,6 +276,34 @@ def attn_decode_append(qkv, kc, vc, pos_t, H: int, G: int):
     """Append the rows' new K/V to the caches at ``pos_t`` and attend over pos + 1 keys."""
     load_ext(required=True)
     return _k().attn_decode_append(qkv, kc, vc, pos_t, H, G)
+
+
+def _decode_kernel(t, hd: int) -> bool:
+    return t.device.type == "cuda" and t.dtype in (torch.bfloat16, torch.float16) and hd in (64, 128)
+
+
+def attn_decode_append_rows(qkv, kc, vc, pos, H: int, G: int):
+    """``attn_decode_append`` with a position per batch row (``pos`` int32 [B] on qkv's device):
+    row b appends its K/V at cache row ``pos[b]`` and attends over keys 0..pos[b].  bf16 / fp16
+    with head dim 64 / 128 run the HIP kernel (no host read: graph-capturable); CPU tensors, fp32
+    and other head dims go to the oracle, as in ``attn_decode``."""
+    if _decode_kernel(qkv, kc.shape[3]):
+        load_ext(required=True)
+        return _k().attn_decode_append_rows(qkv, kc, vc, pos, H, G)
+    return ref.attn_decode_append_rows(qkv, kc, vc, pos, H, G)
+
+
+def kv_cache_fill_varlen(qkv, cu, kc, vc):
+    """Fill the caches [B, G, Tmax, hd] from a packed batch: sequence b is rows [cu[b], cu[b+1]) of
+    qkv [N, (H+2G)*hd] (``cu`` int32 [B + 1] on qkv's device, every length <= Tmax -- the caller
+    checks its host bounds); cache rows (b, g, t < len_b) get the K/V of row cu[b] + t, every
+    other cache element stays.  One launch for bf16 / fp16 / fp32 (head rows of whole 16-byte
+    vectors; any other head dim goes to the oracle)."""
+    if qkv.device.type == "cuda" and (kc.shape[3] * kc.element_size()) % 16 == 0:
+        load_ext(required=True)
+        _k().kv_cache_fill_varlen(qkv, cu, kc, vc)
+        return
+    ref.kv_cache_fill_varlen(qkv, cu, kc, vc)
 
 
 def bias_grad_(dy, db, accumulate: bool = False):

@@ -422,6 +422,32 @@ def attn_decode(q, kcache, vcache, L: int):
     return torch.einsum("bhl,bhld->bhd", p, v).reshape(B, H * hd).to(q.dtype)
 
 
+def attn_decode_append_rows(qkv, kcache, vcache, pos, H: int, G: int):
+    """Reference for the per-row decode step: qkv [B, (H+2G)*hd] (one token per row), cache
+    [B,G,Tmax,hd], pos int [B].  Row b's k / v go into cache row pos[b] and its query attends over
+    keys 0..pos[b] -> [B, H*hd]."""
+    B, hd = qkv.shape[0], kcache.shape[3]
+    rows = qkv.view(B, H + 2 * G, hd)
+    out = torch.empty(B, H * hd, dtype=qkv.dtype, device=qkv.device)
+    for b, p in enumerate(int(p) for p in pos.tolist()):
+        kcache[b, :, p] = rows[b, H:H + G]
+        vcache[b, :, p] = rows[b, H + G:]
+        out[b] = attn_decode(rows[b:b + 1, :H], kcache[b:b + 1], vcache[b:b + 1], p + 1)[0]
+    return out
+
+
+def kv_cache_fill_varlen(qkv, cu, kcache, vcache):
+    """Reference for the cache prefill from a packed batch: sequence b is rows [cu[b], cu[b+1]) of
+    qkv [N, (H+2G)*hd]; cache rows (b, g, t < len_b) <- the k / v of row cu[b] + t."""
+    G, hd = kcache.shape[1], kcache.shape[3]
+    rows = qkv.view(qkv.shape[0], -1, hd)
+    H = rows.shape[1] - 2 * G
+    cb = varlen_bounds(cu)
+    for b, (r0, r1) in enumerate(zip(cb[:-1], cb[1:])):
+        kcache[b, :, :r1 - r0] = rows[r0:r1, H:H + G].transpose(0, 1)
+        vcache[b, :, :r1 - r0] = rows[r0:r1, H + G:].transpose(0, 1)
+
+
 # ------------------------------------------------------------------ LoRA (csrc/lora.hip oracle)
 def lora_down(x, ws, c0, lens, ocol, R: int, scale: float = 1.0):
     """out[:, ocol_i : ocol_i + r_i] = scale * x[:, c0_i : c0_i + len_i] @ w_i[:, :len_i]^T"""

@@ -13,6 +13,10 @@ Same contract: sliding window of ``context_size`` tokens, optional top-k thresho
   output is cut at the first all-eos step, so the result is identical): the host never waits
   on the GPU per token, so each token's ~12 launches per layer queue up behind the previous
   token's kernels instead of running while the GPU idles.
+* :func:`generate_ragged` — the batched form for prompts of different lengths (answering a set
+  of instructions): one unpadded prefill of the packed prompts, then a decode step in which
+  every row sits at its own position (``forward_cached_rows``: per-row RoPE / learned positions
+  and the per-row decode-attention kernel) and stops on its own eos.  No sliding window.
 * On the GPU the single-token step (every layer: norm, QKV GEMM, RoPE, K/V append + decode
   attention, projections, MLP, head) is captured ONCE per sample into a HIP graph
   (``torch.cuda.CUDAGraph``) with the position kept in device memory, and replayed per token:
@@ -127,6 +131,119 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, context_size:
                 pos += 1
     model.train(was_training)
     return out[:, :n]
+
+
+class RowsDecodeGraph:
+    """:class:`DecodeGraph` for ``forward_cached_rows``: the positions are an int32 [B] vector in
+    device memory that the replayed step reads and :meth:`step` advances there.  Captured with
+    every position at the cache's last slot, as ``DecodeGraph`` does."""
+
+    def __init__(self, model, cache, pos: torch.Tensor, device):
+        B, Tmax = pos.numel(), cache[0][0].shape[2]
+        self.idx = torch.zeros(B, 1, dtype=torch.long, device=device)
+        self.pos = torch.full((B,), Tmax - 1, dtype=torch.int32, device=device)
+        cur = torch.cuda.current_stream(device)
+        side = torch.cuda.Stream(device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                model.forward_cached_rows(self.idx, cache, self.pos)
+        cur.wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            self.logits = model.forward_cached_rows(self.idx, cache, self.pos)
+        self.pos.copy_(pos)
+
+    def step(self, idx_next: torch.Tensor) -> torch.Tensor:
+        self.idx.copy_(idx_next)
+        self.graph.replay()
+        self.pos.add_(1)
+        return self.logits
+
+
+@torch.no_grad()
+def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temperature: float = 0.0,
+                    top_k: Optional[int] = None, eos_id: Optional[int] = None,
+                    generator: Optional[torch.Generator] = None) -> list:
+    """Batched KV-cache generation from prompts of different lengths.
+
+    ``prompts``: a non-empty list of non-empty 1-D LongTensors.  Returns one 1-D tensor per prompt:
+    the prompt followed by that row's new tokens up to, not including, its first ``eos_id``, at
+    most ``max_new_tokens`` of them.  A row stops on its own eos (unlike :func:`generate_cached`,
+    which stops when every row emits eos at the same step); the loop ends once every row has.
+
+    ``max(len) + max_new_tokens <= context_size <= the model's context length`` is required
+    (ValueError otherwise, before any device work): there is no sliding window here, and this
+    check is what keeps every device-side position inside the KV cache and the position tables.
+
+    One unpadded prefill of the packed prompts (``forward_prefill_ragged``), then one
+    ``forward_cached_rows`` step per token, with the positions and the finished mask in device
+    memory: the host reads the mask every ``EOS_CHECK_EVERY`` tokens and never waits per token.
+    On the GPU the step is captured once into a HIP graph and replayed (``BLLM_DECODE_GRAPH=0``:
+    eager), as in :func:`generate_cached`.
+
+    Greedy (``temperature == 0``): row b is what ``generate_cached(model, prompts[b][None], ...)``
+    gives alone, up to GEMM rounding.  Sampling draws ONE multinomial over the [B, V]
+    probabilities per step, so a row's draws depend on which rows share its batch."""
+    from ..models.base import pack_prompts
+    if not isinstance(prompts, (list, tuple)) or len(prompts) == 0:
+        raise ValueError("generate_ragged: prompts must be a non-empty list of 1-D token tensors")
+    for b, p in enumerate(prompts):
+        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() == 0 or p.dtype != torch.long:
+            raise ValueError(f"generate_ragged: prompt {b} must be a non-empty 1-D LongTensor")
+    lens = [int(p.numel()) for p in prompts]
+    new = max(int(max_new_tokens), 0)
+    if max(lens) + new > context_size:
+        raise ValueError(f"generate_ragged: the longest prompt ({max(lens)} tokens) + max_new_tokens ({new}) "
+                         f"exceeds context_size ({context_size}); this path has no sliding window")
+    if context_size > model.cfg.context_length:
+        raise ValueError(f"generate_ragged: context_size ({context_size}) exceeds the model's context length "
+                         f"({model.cfg.context_length})")
+    device = next(model.parameters()).device
+    if new == 0:
+        return [p.to(device) for p in prompts]
+    was_training = model.training
+    model.eval()
+    B = len(prompts)
+    idx, seq = pack_prompts(prompts, device)
+    out = torch.zeros(B, new, dtype=torch.long, device=device)
+    pos = torch.tensor(lens, dtype=torch.int32).to(device)           # row b's next position
+    finished = torch.zeros(B, dtype=torch.bool, device=device)
+    n = checked = 0
+    eng = model.rctx.engine
+    resident = eng.params_resident() if hasattr(eng, "params_resident") else _null()
+    with resident:
+        cache = model.new_kv_cache(B, context_size)
+        logits = model.forward_prefill_ragged(idx, seq, cache)
+        dec = None
+        if new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
+            logits = logits.clone()            # the prefill output must survive the capture
+            dec = RowsDecodeGraph(model, cache, pos, device)
+        for i in range(new):
+            idx_next = _sample(logits, temperature, top_k, generator)
+            out[:, i] = idx_next[:, 0]
+            n = i + 1
+            if n == new:
+                break
+            if eos_id is not None:
+                finished |= idx_next[:, 0] == eos_id
+                if n - checked >= EOS_CHECK_EVERY:
+                    if bool(finished.all()):   # tokens after a row's first eos are dropped below
+                        break
+                    checked = n
+            if dec is not None:
+                logits = dec.step(idx_next)
+            else:
+                logits = model.forward_cached_rows(idx_next, cache, pos)
+                pos += 1
+    gen = out[:, :n]
+    if eos_id is not None:
+        is_eos = gen == eos_id
+        keep = torch.where(is_eos.any(dim=1), is_eos.to(torch.int64).argmax(dim=1), n).tolist()
+    else:
+        keep = [n] * B
+    model.train(was_training)
+    return [torch.cat((idx[seq.bounds[b]:seq.bounds[b + 1]], gen[b, :keep[b]])) for b in range(B)]
 
 
 class _null:

@@ -33,7 +33,7 @@ from ..utils.misc import read_json_file, read_text_file, text_to_token_ids, toke
 from ..data.datasets import unpad_lengths
 from ..data.loaders import first_batches
 from .checkpoint import resume_state_path, save_model, save_resume_state
-from .generate import generate_cached
+from .generate import generate_cached, generate_ragged
 
 IGNORE_INDEX = -100   # the instruction collate's masked-target id (data/datasets.py)
 
@@ -494,6 +494,32 @@ class Trainer:
         if self.rank == 0 and memory_check:
             logger.info(f"Generated Sample: {decoded.replace(chr(10), ' ')}")
         return decoded
+
+    def generate_responses(self, prompts, max_new_tokens: int, batch_size: int):
+        """Greedy continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in
+        input order, each cut before its first eos.  The prompts are sorted by token count and cut
+        into batches of ``batch_size``, so a batch's rows have similar lengths, and every batch is
+        one :func:`generate_ragged` call.  Every rank must call this with the same prompts (the
+        engines gather parameters collectively, as for the sample print).  A prompt longer than
+        ``context_length - max_new_tokens`` raises ValueError naming its index, before any
+        generation."""
+        tok, cfg = self.loaderObj.tokenizer, self.config
+        ctx = cfg["context_length"]
+        ids = [text_to_token_ids(t, tok, cfg)[0] for t in prompts]
+        for i, t in enumerate(ids):
+            if t.numel() == 0:
+                raise ValueError(f"prompt {i} is empty after tokenisation")
+            if t.numel() + max_new_tokens > ctx:
+                raise ValueError(f"prompt {i} has {t.numel()} tokens: with max_new_tokens {max_new_tokens} it does "
+                                 f"not fit the context length {ctx}")
+        order = sorted(range(len(ids)), key=lambda i: ids[i].numel())
+        out = [None] * len(ids)
+        for s in range(0, len(order), max(1, int(batch_size))):
+            rows = order[s:s + max(1, int(batch_size))]
+            res = generate_ragged(self.model, [ids[i] for i in rows], max_new_tokens, ctx, eos_id=cfg["eos_id"])
+            for i, r in zip(rows, res):
+                out[i] = tok.decode(r[ids[i].numel():].tolist())
+        return out
 
     def save_checkpoint(self, file_name):
         self._flush_tokens()   # the resume state carries the exact all-rank count

@@ -137,6 +137,14 @@ void attn_decode_append(DType dt, const void* qkv, void* kc, void* vc, void* out
                         int G, int hd, int Tmax, hipStream_t s);
 void attn_decode(DType dt, const void* q, const void* kc, const void* vc, void* out, int B, int H, int G, int hd,
                  int Tmax, int L, hipStream_t s);
+// attn_decode_append with one position per batch row (pos int32 [B]): row b appends at pos[b] and
+// attends over its pos[b] + 1 keys (decode of a ragged batch)
+void attn_decode_append_rows(DType dt, const void* qkv, void* kc, void* vc, void* out, const int* pos, int B, int H,
+                             int G, int hd, int Tmax, hipStream_t s);
+// caches from a packed variable-length batch: cache row (b, g, t) <- k / v of qkv row cu[b] + t
+// (cu int32 [B + 1] on the device, every length <= Tmax); row_bytes = hd * element size, whole 16 B
+void kv_cache_fill_varlen(const void* qkv, const int* cu, void* kc, void* vc, long N, int B, int H, int G, int Tmax,
+                          int row_bytes, hipStream_t s);
 
 // loss.hip
 void ce_fwd(DType dt, const void* logits, const int64_t* tgt, float* loss, float* lse, long N, long V, long ld,

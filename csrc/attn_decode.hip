@@ -22,110 +22,61 @@ BLLM_DEBUG_WORD(attn_decode)
 constexpr int DEC_THREADS = 256;
 constexpr int DEC_MAXL = 8192;  // LDS score buffer (32 KiB)
 
+// Three forms share one body (attn_decode_body.h):
+// plain: q [B, H, hd] against the first L cached positions.
 // APPEND (graph-replayed decode, the position known only on the device): q, the new key and
 // the new value come from the packed qkv row of the token (row stride qs); L = *pos + 1 and key
 // L - 1 is read from that row, while the first query head of each kv group also writes it into
 // the caches at row *pos (no block of this launch reads cache row *pos, so no ordering needed).
+// rows (attn_decode_rows_k, decode of a ragged batch): APPEND with one position per batch row;
+// row b appends at cache row pos[b] and attends over its own pos[b] + 1 keys.
 template <typename T, int HD, bool APPEND>
 __global__ __launch_bounds__(DEC_THREADS) void attn_decode_k(const T* __restrict__ q, T* __restrict__ kc,
                                                              T* __restrict__ vc, T* __restrict__ out,
                                                              int H, int G, int Tmax, int L, float scale,
                                                              const int* __restrict__ pos, long qs) {
-  constexpr int VEC = 8;               // elements per 16-B load
-  constexpr int NC = HD / VEC;         // 16-B chunks per row
-  constexpr int KPH = DEC_THREADS / NC;  // key phases in the output pass
-  __shared__ float sc[DEC_MAXL];
-  __shared__ float red[DEC_THREADS / 64];
-  __shared__ float part[KPH][HD];
-  const int bh = blockIdx.x, h = bh % H, b = bh / H;
-  const int g = h / (H / G);
-  const int tid = threadIdx.x;
-  const T* qr = APPEND ? q + (long)b * qs + (long)h * HD : q + ((long)b * H + h) * HD;
-  T* kb = kc + ((long)b * G + g) * (long)Tmax * HD;
-  T* vb = vc + ((long)b * G + g) * (long)Tmax * HD;
-  const T* knew = nullptr;
-  const T* vnew = nullptr;
-  if constexpr (APPEND) {
-    int p = *pos;
-    BLLM_DASSERT(p >= 0 && p < Tmax && p < DEC_MAXL, DBG_DECODE_POS);
-#ifdef BLLM_KERNEL_DEBUG
-    p = p < 0 ? 0 : (p >= Tmax ? Tmax - 1 : p);
-    p = p >= DEC_MAXL ? DEC_MAXL - 1 : p;
-#endif
-    L = p + 1;
-    knew = q + (long)b * qs + (long)(H + g) * HD;
-    vnew = q + (long)b * qs + (long)(H + G + g) * HD;
-    if (h % (H / G) == 0 && tid < 2 * (HD / 8)) {  // one block per kv group appends k and v
-      const int c = tid % (HD / 8);
-      if (tid < HD / 8) st16(kb + (long)p * HD + c * 8, ld16(knew + c * 8));
-      else st16(vb + (long)p * HD + c * 8, ld16(vnew + c * 8));
-    }
-  }
-  const float c = scale * kLog2e;
+#define DEC_POS(b) (*pos)
+#include "attn_decode_body.h"
+#undef DEC_POS
+}
 
-  float qf[HD];
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    const Vec16<T> v = ld16(qr + i * VEC);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) qf[i * VEC + j] = to_f(v.v[j]);
+template <typename T, int HD>
+__global__ __launch_bounds__(DEC_THREADS) void attn_decode_rows_k(const T* __restrict__ q, T* __restrict__ kc,
+                                                                  T* __restrict__ vc, T* __restrict__ out,
+                                                                  int H, int G, int Tmax, float scale,
+                                                                  const int* __restrict__ pos, long qs) {
+  constexpr bool APPEND = true;
+  int L = 0;
+#define DEC_POS(b) (pos[b])
+#include "attn_decode_body.h"
+#undef DEC_POS
+}
+
+// Prefill of the caches from a packed variable-length batch: cache row (b, g, t) <- the k and v
+// of packed row cu[b] + t.  One thread per 16-B chunk of one (row, k-or-v head); the row's
+// sequence is found by bisection of cu (B + 1 entries, read through the scalar cache).  C =
+// chunks per head row, qsc = chunks per qkv row.  Any element type: the copy is bitwise.
+__global__ __launch_bounds__(256) void kv_cache_fill_varlen_k(const uint4* __restrict__ qkv,
+                                                              const int* __restrict__ cu, uint4* __restrict__ kc,
+                                                              uint4* __restrict__ vc, long N, int B, int H, int G,
+                                                              int Tmax, int C, long qsc) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long per_row = 2L * G * C;
+  if (i >= N * per_row) return;
+  const long n = i / per_row;
+  const int j = (int)((i % per_row) / C), c = (int)(i % C);  // j: k heads 0..G-1, then v heads
+  if (n < cu[0] || n >= cu[B]) return;                        // rows outside every sequence
+  int lo = 0, hi = B;                                         // cu[lo] <= n < cu[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu[mid] <= n) lo = mid; else hi = mid;
   }
-  // 1. scores (log2 domain)
-  float mx = -INFINITY;
-  for (int k = tid; k < L; k += DEC_THREADS) {
-    const T* kr = (APPEND && k == L - 1) ? knew : kb + (long)k * HD;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-      const Vec16<T> v = ld16(kr + i * VEC);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) s += qf[i * VEC + j] * to_f(v.v[j]);
-    }
-    s *= c;
-    sc[k] = s;
-    mx = fmaxf(mx, s);
-  }
-  // 2. softmax statistics
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int i = 1; i < DEC_THREADS / 64; ++i) mx = fmaxf(mx, red[i]);
-  __syncthreads();
-  float sum = 0.f;
-  for (int k = tid; k < L; k += DEC_THREADS) {
-    const float p = exp2f(sc[k] - mx);
-    sc[k] = p;
-    sum += p;
-  }
-  sum = wave_sum(sum);
-  if ((tid & 63) == 0) red[tid >> 6] = sum;
-  __syncthreads();
-  sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < DEC_THREADS / 64; ++i) sum += red[i];
-  const float inv = 1.f / sum;
-  // 3. weighted V sum: thread = (chunk ci, key phase kp)
-  const int ci = tid % NC, kp = tid / NC;
-  float acc[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
-  for (int k = kp; k < L; k += KPH) {
-    const Vec16<T> v = ld16(((APPEND && k == L - 1) ? vnew : vb + (long)k * HD) + ci * VEC);
-    const float p = sc[k];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) acc[j] += p * to_f(v.v[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) part[kp][ci * VEC + j] = acc[j];
-  __syncthreads();
-  for (int d = tid; d < HD; d += DEC_THREADS) {
-    float o = 0.f;
-#pragma unroll
-    for (int p2 = 0; p2 < KPH; ++p2) o += part[p2][d];
-    out[((long)b * H + h) * HD + d] = from_f<T>(o * inv);
-  }
+  const int t = (int)(n - cu[lo]);
+  BLLM_DASSERT(t < Tmax, DBG_DECODE_POS);
+  if (t >= Tmax) return;
+  const int g = j < G ? j : j - G;
+  uint4* dst = (j < G ? kc : vc) + (((long)lo * G + g) * Tmax + t) * C + c;
+  *dst = qkv[n * qsc + (long)(H + j) * C + c];
 }
 
 int attn_decode_max_len() { return DEC_MAXL; }
@@ -157,6 +108,30 @@ void attn_decode_append(DType dt, const void* qkv, void* kc, void* vc, void* out
     if (hd == 128) L_(f16_t, 128); else L_(f16_t, 64);
   }
 #undef L_
+}
+
+void attn_decode_append_rows(DType dt, const void* qkv, void* kc, void* vc, void* out, const int* pos, int B, int H,
+                             int G, int hd, int Tmax, hipStream_t s) {
+  const float scale = 1.f / sqrtf((float)hd);
+  const long qs = (long)(H + 2 * G) * hd;
+  dim3 grid(B * H), block(DEC_THREADS);
+#define L_(TT, HDD) hipLaunchKernelGGL((attn_decode_rows_k<TT, HDD>), grid, block, 0, s, (const TT*)qkv, (TT*)kc, \
+                                       (TT*)vc, (TT*)out, H, G, Tmax, scale, pos, qs)
+  if (dt == DType::BF16) {
+    if (hd == 128) L_(bf16_t, 128); else L_(bf16_t, 64);
+  } else {
+    if (hd == 128) L_(f16_t, 128); else L_(f16_t, 64);
+  }
+#undef L_
+}
+
+void kv_cache_fill_varlen(const void* qkv, const int* cu, void* kc, void* vc, long N, int B, int H, int G, int Tmax,
+                          int row_bytes, hipStream_t s) {
+  const int C = row_bytes / 16;
+  const long total = N * 2L * G * C;
+  if (total == 0) return;
+  hipLaunchKernelGGL(kv_cache_fill_varlen_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                     (const uint4*)qkv, cu, (uint4*)kc, (uint4*)vc, N, B, H, G, Tmax, C, (long)(H + 2 * G) * C);
 }
 
 }  // namespace bllm

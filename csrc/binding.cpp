@@ -656,6 +656,49 @@ Tensor attn_decode_append(const Tensor& qkv, Tensor& kc, Tensor& vc, const Tenso
   return out;
 }
 
+// attn_decode_append with a position per batch row: pos int32 [B], row b appends at pos[b] and
+// attends over pos[b] + 1 keys (the caller keeps every pos[b] < Tmax)
+Tensor attn_decode_append_rows(const Tensor& qkv, Tensor& kc, Tensor& vc, const Tensor& pos, int64_t H, int64_t G) {
+  Op op("attn_decode_append_rows", qkv, "qkv");
+  op.dims(qkv, 2, "qkv");
+  op.dims(kc, 4, "kcache");
+  const int64_t B = qkv.size(0), hd = kc.size(3), Tmax = kc.size(2);
+  decode_caches(op, qkv, kc, vc, B, H, hd);
+  TORCH_CHECK(kc.size(1) == G && qkv.size(1) == (H + 2 * G) * hd, "attn_decode_append_rows: qkv ", qkv.sizes(),
+              " / cache ", kc.sizes(), " mismatch for H ", H, " G ", G);
+  TORCH_CHECK(Tmax >= 1 && Tmax <= bllm::attn_decode_max_len(),
+              "attn_decode_append_rows: cache empty or longer than the LDS score buffer");
+  op.vec(pos, B, at::kInt, "pos");
+  auto out = at::empty({B, H * hd}, qkv.options());
+  bllm::attn_decode_append_rows(dt_of(qkv), qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                                pos.data_ptr<int>(), op.to_int(B, "B"), op.to_int(H, "H"), op.to_int(G, "G"),
+                                op.to_int(hd, "hd"), op.to_int(Tmax, "Tmax"), stream());
+  return out;
+}
+
+// qkv [N, (H+2G)*hd] packed rows, sequence b = rows [cu[b], cu[b+1]) (cu int32 [B+1], lengths
+// <= Tmax: the caller's host bounds); kc / vc [B, G, Tmax, hd]: rows t < len_b of (b, g) <- the k / v
+// of qkv row cu[b] + t, nothing else written
+void kv_cache_fill_varlen(const Tensor& qkv, const Tensor& cu, Tensor& kc, Tensor& vc) {
+  Op op("kv_cache_fill_varlen", qkv, "qkv");
+  op.dense(qkv, "qkv");
+  op.dims(qkv, 2, "qkv");
+  op.dims(kc, 4, "kcache");
+  const int64_t N = qkv.size(0), B = kc.size(0), G = kc.size(1), Tmax = kc.size(2), hd = kc.size(3);
+  op.shaped(kc, {B, G, Tmax, hd}, qkv.scalar_type(), "kcache");
+  op.like(vc, kc, "vcache");
+  const int64_t row_bytes = hd * qkv.element_size();
+  TORCH_CHECK(B > 0 && G > 0 && Tmax > 0 && hd > 0 && row_bytes % 16 == 0 && aligned(qkv, 16) && aligned(kc, 16) &&
+                  aligned(vc, 16),
+              "kv_cache_fill_varlen: cache ", kc.sizes(), " must be non-empty with 16-byte aligned head rows");
+  TORCH_CHECK(qkv.size(1) % hd == 0 && qkv.size(1) / hd > 2 * G, "kv_cache_fill_varlen: qkv ", qkv.sizes(),
+              " is not [N, (H + 2G) hd] for the cache's G ", G, " and hd ", hd);
+  op.vec(cu, B + 1, at::kInt, "cu");
+  bllm::kv_cache_fill_varlen(qkv.data_ptr(), cu.data_ptr<int>(), kc.data_ptr(), vc.data_ptr(), N, op.to_int(B, "B"),
+                             op.to_int(qkv.size(1) / hd - 2 * G, "H"), op.to_int(G, "G"), op.to_int(Tmax, "Tmax"),
+                             op.to_int(row_bytes, "row bytes"), stream());
+}
+
 // q [B, H, hd]; kc / vc [B, G, Tmax, hd] with the first L positions valid -> out [B, H*hd]
 Tensor attn_decode(const Tensor& q, const Tensor& kc, const Tensor& vc, int64_t L) {
   Op op("attn_decode", q, "q");
@@ -1290,6 +1333,8 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("gemm_nt_bias_gelu_(Tensor a, Tensor w, Tensor bias, Tensor(a!) f, Tensor(b!) g) -> ()", gemm_nt_bias_gelu_);
   BLLM_OP("attn_decode(Tensor q, Tensor kcache, Tensor vcache, int L) -> Tensor", attn_decode);
   BLLM_OP("attn_decode_append(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append);
+  BLLM_OP("attn_decode_append_rows(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_rows);
+  BLLM_OP("kv_cache_fill_varlen(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) vcache) -> ()", kv_cache_fill_varlen);
   BLLM_OP("rope_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, int H, int G, int hd, Tensor pos) -> ()", rope_dev_);
   BLLM_OP("rope_pos_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos_ids, int H, int G, int hd, bool inverse) -> ()", rope_pos_);
   BLLM_OP("flash_attn_varlen_fwd(Tensor qkv, Tensor cu, int max_len, int H, int G, int hd) -> (Tensor, Tensor)", flash_attn_varlen_fwd);

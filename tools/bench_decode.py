@@ -2,10 +2,20 @@
 """Sampling / decode benchmark (GPU): the Trainer's sample print (reference train.py:213-229:
 200 new tokens, top-k 5, temperature 1) on random-init weights, KV-cache decode
 (train/generate.py:generate_cached).  Prints ms per generated token and tokens/s.
-Usage: python tools/bench_decode.py [--model llama3 --num_params 8B] [--tokens 200] [--graph 0|1]"""
+Usage: python tools/bench_decode.py [--model llama3 --num_params 8B] [--tokens 200] [--graph 0|1]
+
+``--ragged B1,B2,...``: answering B instructions.  The prompts are the first B records of the
+synthetic Alpaca file in the ``--finetune`` prompt format, tokenised with the model's tokenizer;
+``generate_ragged`` on all B (A) against B one-row ``generate_cached`` runs over the same prompts
+(B, the only way before), greedy without eos, ``--tokens`` new tokens each, in one process,
+interleaved A B A B, ``--repeats`` times after one warm-up of each.  Per batch size one JSON line
+(and one entry of ``--out FILE``): median and range of ms per generated token (wall time over
+all B x tokens tokens) and responses/s.
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128"""
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -18,6 +28,67 @@ from building_llm_from_scratch_amd.models import build_model  # noqa: E402
 from building_llm_from_scratch_amd.train import generate as G  # noqa: E402
 
 
+def _alpaca_prompts(model, cfg, n):
+    from building_llm_from_scratch_amd.data.datasets import format_input
+    from building_llm_from_scratch_amd.data.synthetic import alpaca_records
+    from building_llm_from_scratch_amd.data.tokenizer import build_tokenizer
+    tok = build_tokenizer(model, cfg)
+    texts = [format_input(r) + "\n\n### Response:\n" for r in alpaca_records(n)]
+    return [torch.tensor(tok.encode(t), dtype=torch.long) for t in texts], getattr(tok, "name", type(tok).__name__)
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def _stats(times, B, tokens):
+    ms = sorted(1000 * t / (B * tokens) for t in times)
+    rs = sorted(B / t for t in times)
+    return {"ms_per_token": round(statistics.median(ms), 4), "ms_per_token_range": [round(ms[0], 4), round(ms[-1], 4)],
+            "responses_per_s": round(statistics.median(rs), 2),
+            "responses_per_s_range": [round(rs[0], 2), round(rs[-1], 2)]}
+
+
+def ragged(a, m, cfg):
+    sizes = [int(b) for b in a.ragged.split(",")]
+    prompts, tok_name = _alpaca_prompts(a.model, cfg, max(sizes))
+    ctx = cfg.context_length
+    rows = []
+    for B in sizes:
+        ps = prompts[:B]
+
+        def run_ragged():
+            return G.generate_ragged(m, ps, a.tokens, ctx)
+
+        def run_rows():
+            return [G.generate_cached(m, p[None], a.tokens, ctx) for p in ps]
+
+        run_ragged()
+        run_rows()
+        ta, tb = [], []
+        for _ in range(a.repeats):
+            ta.append(_timed(run_ragged))
+            tb.append(_timed(run_rows))
+        lens = [int(p.numel()) for p in ps]
+        row = {"model": f"{a.model}-{a.num_params}", "batch": B, "new_tokens": a.tokens, "repeats": a.repeats,
+               "tokenizer": tok_name, "prompt_tokens": {"min": min(lens), "max": max(lens), "sum": sum(lens)},
+               "graph": os.environ.get("BLLM_DECODE_GRAPH", "default"),
+               "generate_ragged": _stats(ta, B, a.tokens), "generate_cached_rows": _stats(tb, B, a.tokens)}
+        row["speedup"] = round(row["generate_cached_rows"]["ms_per_token"] / row["generate_ragged"]["ms_per_token"], 2)
+        lo, hi = row["generate_cached_rows"]["ms_per_token_range"]
+        row["ragged_inside_rows_range"] = lo <= row["generate_ragged"]["ms_per_token"] <= hi
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3")
@@ -26,6 +97,9 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--prompt", type=int, default=6)
     ap.add_argument("--graph", type=int, default=None, help="force the hipGraph decode step on/off")
+    ap.add_argument("--ragged", default=None, help="comma list of batch sizes: generate_ragged vs one-row runs")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None, help="--ragged: also write the rows to this JSON file")
     a = ap.parse_args()
     ops.load_ext(required=True)
     cfg = get_config(a.model, a.num_params).replace(dtype=torch.bfloat16)
@@ -34,6 +108,8 @@ def main():
     m.flatten()
     if a.graph is not None:
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
+    if a.ragged:
+        return ragged(a, m, cfg)
     idx = torch.randint(0, cfg.vocab_size, (a.batch, a.prompt), device="cuda")
     g = torch.Generator(device="cuda").manual_seed(1)
     G.generate_cached(m, idx, 8, cfg.context_length, temperature=1.0, top_k=5, generator=g)  # warm-up
