@@ -234,7 +234,8 @@ def cached_attention(qkv, B: int, t: int, pos: int, H: int, G: int, hd: int, kv,
     """Attention of ``t`` new tokens at positions ``pos..pos+t-1`` (packed qkv rows, RoPE
     already applied) against a per-block KV cache ``kv = (k, v)`` of [B, G, Tmax, hd]; the new
     keys/values are appended to the cache first.  Prefill from position 0 runs the flash kernel
-    on the packed rows; single-token decode runs the HIP decode kernel over the cache."""
+    on the packed rows; single-token decode runs the HIP decode kernel over the cache (past
+    ``ops.DECODE_SPLIT_MIN`` keys the split-KV one, so the cache may be as long as the context)."""
     from .. import ops
     kc, vc = kv
     rows = qkv.view(B, t, H + 2 * G, hd)
@@ -589,11 +590,12 @@ class BaseLM(nn.Module):
 
     def decode_graph_ok(self, cache) -> bool:
         """Whether :meth:`forward_cached_dev` runs on this model / cache (GPU, bf16/fp16, head
-        dim 64/128, cache <= 8192 positions)."""
+        dim 64/128; any cache length: past ``ops.DECODE_SPLIT_MIN`` positions the split-KV
+        decode kernel takes over)."""
         dev = self._anchor.device if self._anchor is not None else torch.device("cpu")
         kc = cache[0][0]
         return (dev.type == "cuda" and kc.dtype in (torch.bfloat16, torch.float16)
-                and self.cfg.head_dim in (64, 128) and kc.shape[2] <= 8192)
+                and self.cfg.head_dim in (64, 128))
 
     @torch.no_grad()
     def forward_cached_dev(self, idx: torch.Tensor, cache, pos_t: torch.Tensor) -> torch.Tensor:

@@ -272,9 +272,18 @@ def rope_dev_(qkv, cos, sin, H: int, G: int, hd: int, pos_t):
     return qkv
 
 
+# Caches longer than this run the split-KV kernels (csrc/attn_decode_split.hip: key chunks in
+# parallel, then a merge); up to it the single-launch kernels of csrc/attn_decode.hip, whose LDS
+# score buffer holds at most this many keys.
+DECODE_SPLIT_MIN = 8192
+
+
 def attn_decode_append(qkv, kc, vc, pos_t, H: int, G: int):
-    """Append the rows' new K/V to the caches at ``pos_t`` and attend over pos + 1 keys."""
+    """Append the rows' new K/V to the caches at ``pos_t`` and attend over pos + 1 keys (caches
+    of more than ``DECODE_SPLIT_MIN`` positions: the split-KV kernel)."""
     load_ext(required=True)
+    if kc.shape[2] > DECODE_SPLIT_MIN:
+        return _k().attn_decode_append_split(qkv, kc, vc, pos_t, H, G)
     return _k().attn_decode_append(qkv, kc, vc, pos_t, H, G)
 
 
@@ -285,10 +294,13 @@ def _decode_kernel(t, hd: int) -> bool:
 def attn_decode_append_rows(qkv, kc, vc, pos, H: int, G: int):
     """``attn_decode_append`` with a position per batch row (``pos`` int32 [B] on qkv's device):
     row b appends its K/V at cache row ``pos[b]`` and attends over keys 0..pos[b].  bf16 / fp16
-    with head dim 64 / 128 run the HIP kernel (no host read: graph-capturable); CPU tensors, fp32
-    and other head dims go to the oracle, as in ``attn_decode``."""
+    with head dim 64 / 128 run the HIP kernel (no host read: graph-capturable; caches of more than
+    ``DECODE_SPLIT_MIN`` positions the split-KV one); CPU tensors, fp32 and other head dims go to
+    the oracle, as in ``attn_decode``."""
     if _decode_kernel(qkv, kc.shape[3]):
         load_ext(required=True)
+        if kc.shape[2] > DECODE_SPLIT_MIN:
+            return _k().attn_decode_append_split(qkv, kc, vc, pos, H, G)
         return _k().attn_decode_append_rows(qkv, kc, vc, pos, H, G)
     return ref.attn_decode_append_rows(qkv, kc, vc, pos, H, G)
 
@@ -600,9 +612,12 @@ def sum_partials_(part, out, accumulate: bool = False):
 
 def attn_decode(q, kcache, vcache, L: int):
     """One new query per sequence against the first ``L`` cached positions.
-    q [B, H, hd]; kcache / vcache [B, G, Tmax, hd] -> [B, H*hd]."""
+    q [B, H, hd]; kcache / vcache [B, G, Tmax, hd] -> [B, H*hd].  More than ``DECODE_SPLIT_MIN``
+    positions run the split-KV kernel."""
     if q.device.type == "cuda" and q.dtype in (torch.bfloat16, torch.float16):
         load_ext(required=True)
+        if int(L) > DECODE_SPLIT_MIN:
+            return _k().attn_decode_split(q.contiguous(), kcache, vcache, int(L))
         return _k().attn_decode(q.contiguous(), kcache, vcache, int(L))
     return ref.attn_decode(q, kcache, vcache, L)
 

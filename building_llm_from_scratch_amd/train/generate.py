@@ -17,6 +17,9 @@ Same contract: sliding window of ``context_size`` tokens, optional top-k thresho
   of instructions): one unpadded prefill of the packed prompts, then a decode step in which
   every row sits at its own position (``forward_cached_rows``: per-row RoPE / learned positions
   and the per-row decode-attention kernel) and stops on its own eos.  No sliding window.
+* The cache may be as long as the model's context: decode attention over more than
+  ``ops.DECODE_SPLIT_MIN`` (8,192) cached positions runs the split-KV kernels
+  (``csrc/attn_decode_split.hip``), eagerly and inside the captured step alike.
 * On the GPU the single-token step (every layer: norm, QKV GEMM, RoPE, K/V append + decode
   attention, projections, MLP, head) is captured ONCE per sample into a HIP graph
   (``torch.cuda.CUDAGraph``) with the position kept in device memory, and replayed per token:
@@ -53,7 +56,10 @@ def _graph_enabled() -> bool:
 class DecodeGraph:
     """A model's single-token decode step (``forward_cached_dev``) captured into a HIP graph.
     Capture runs with the position set to the cache's LAST slot, so the warm-up / capture
-    passes only write that slot, which every later decode step overwrites before reading it."""
+    passes only write that slot, which every later decode step overwrites before reading it.
+    They also READ the whole cache, which at this point is uninitialised beyond the prompt (at a
+    long context most of it): their output is discarded, and the decode kernels do not care
+    what the values are (NaNs included) -- they only must not be used."""
 
     def __init__(self, model, cache, B: int, device):
         Tmax = cache[0][0].shape[2]

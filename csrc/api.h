@@ -12,6 +12,7 @@ namespace bllm {
 unsigned int debug_take_embedding();
 unsigned int debug_take_loss();
 unsigned int debug_take_attn_decode();
+unsigned int debug_take_attn_decode_split();
 unsigned int debug_take_elementwise();
 
 // norms.hip
@@ -145,6 +146,17 @@ void attn_decode_append_rows(DType dt, const void* qkv, void* kc, void* vc, void
 // (cu int32 [B + 1] on the device, every length <= Tmax); row_bytes = hd * element size, whole 16 B
 void kv_cache_fill_varlen(const void* qkv, const int* cu, void* kc, void* vc, long N, int B, int H, int G, int Tmax,
                           int row_bytes, hipStream_t s);
+
+// attn_decode_split.hip — the same attention in two launches (per key chunk, then a merge), for
+// caches of any length.  ws: fp32 scratch of attn_decode_split_workspace(B, H, hd, Tmax) floats,
+// chunk count fixed by Tmax.  pos_stride 0: one shared position (*pos), 1: a position per row.
+int attn_decode_split_chunk();
+long attn_decode_split_workspace(int B, int H, int hd, int Tmax);
+bool attn_decode_split_grid_ok(int B, int H, int G);
+void attn_decode_split(DType dt, const void* q, const void* kc, const void* vc, void* out, float* ws, int B, int H,
+                       int G, int hd, int Tmax, int L, hipStream_t s);
+void attn_decode_append_split(DType dt, const void* qkv, void* kc, void* vc, void* out, float* ws, const int* pos,
+                              int pos_stride, int B, int H, int G, int hd, int Tmax, hipStream_t s);
 
 // loss.hip
 void ce_fwd(DType dt, const void* logits, const int64_t* tgt, float* loss, float* lse, long N, long V, long ld,

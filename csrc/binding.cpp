@@ -714,6 +714,61 @@ Tensor attn_decode(const Tensor& q, const Tensor& kc, const Tensor& vc, int64_t 
   return out;
 }
 
+// Split-KV forms of the two ops above (csrc/attn_decode_split.hip): any cache length, the key
+// chunks fixed by Tmax.  The scratch of per-chunk partials is allocated here per call (under graph
+// capture it belongs to the graph's pool); the merge reads only the slots this call wrote.
+Tensor decode_split_scratch(const Op& op, const Tensor& q, int64_t B, int64_t H, int64_t G, int64_t hd,
+                            int64_t Tmax) {
+  TORCH_CHECK(Tmax >= 1, op.name, ": empty cache");
+  op.to_int(Tmax, "Tmax");
+  TORCH_CHECK(bllm::attn_decode_split_grid_ok(op.to_int(B, "B"), op.to_int(H, "H"), op.to_int(G, "G")), op.name,
+              ": B ", B, " or the cache's G ", G, " exceeds the launch grid");
+  return at::empty({bllm::attn_decode_split_workspace((int)B, (int)H, (int)hd, (int)Tmax)},
+                   q.options().dtype(at::kFloat));
+}
+
+// attn_decode_append / attn_decode_append_rows in one: pos int32 with 1 element (a position
+// shared by the rows) or B elements (one per row; the caller keeps every position < Tmax)
+Tensor attn_decode_append_split(const Tensor& qkv, Tensor& kc, Tensor& vc, const Tensor& pos, int64_t H, int64_t G) {
+  Op op("attn_decode_append_split", qkv, "qkv");
+  op.dims(qkv, 2, "qkv");
+  op.dims(kc, 4, "kcache");
+  const int64_t B = qkv.size(0), hd = kc.size(3), Tmax = kc.size(2);
+  decode_caches(op, qkv, kc, vc, B, H, hd);
+  TORCH_CHECK(kc.size(1) == G && qkv.size(1) == (H + 2 * G) * hd, "attn_decode_append_split: qkv ", qkv.sizes(),
+              " / cache ", kc.sizes(), " mismatch for H ", H, " G ", G);
+  TORCH_CHECK(aligned(qkv, 16) && aligned(kc, 16) && aligned(vc, 16),
+              "attn_decode_append_split: qkv and the caches must be 16-byte aligned");
+  op.contig(pos, "pos");
+  op.dtype(pos, at::kInt, "pos");
+  TORCH_CHECK(pos.numel() == 1 || pos.numel() == B, "attn_decode_append_split: pos must have 1 or ", B,
+              " elements, got ", pos.numel());
+  auto ws = decode_split_scratch(op, qkv, B, H, G, hd, Tmax);
+  auto out = at::empty({B, H * hd}, qkv.options());
+  bllm::attn_decode_append_split(dt_of(qkv), qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                                 ws.data_ptr<float>(), pos.data_ptr<int>(), pos.numel() == 1 ? 0 : 1, (int)B, (int)H,
+                                 (int)G, (int)hd, (int)Tmax, stream());
+  return out;
+}
+
+// q [B, H, hd]; kc / vc [B, G, Tmax, hd] with the first L positions valid -> out [B, H*hd]
+Tensor attn_decode_split(const Tensor& q, const Tensor& kc, const Tensor& vc, int64_t L) {
+  Op op("attn_decode_split", q, "q");
+  op.dims(q, 3, "q");
+  op.dims(kc, 4, "kcache");
+  const int64_t B = q.size(0), H = q.size(1), hd = q.size(2), G = kc.size(1), Tmax = kc.size(2);
+  decode_caches(op, q, kc, vc, B, H, hd);
+  TORCH_CHECK(aligned(q, 16) && aligned(kc, 16) && aligned(vc, 16),
+              "attn_decode_split: q and the caches must be 16-byte aligned");
+  TORCH_CHECK(L >= 1 && L <= Tmax, "attn_decode_split: bad length ", L);
+  auto ws = decode_split_scratch(op, q, B, H, G, hd, Tmax);
+  auto out = at::empty({B, H * hd}, q.options());
+  bllm::attn_decode_split(dt_of(q), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), ws.data_ptr<float>(),
+                          (int)B, (int)H, (int)G, (int)hd, (int)Tmax, (int)L, stream());
+  return out;
+}
+int64_t attn_decode_split_chunk() { return bllm::attn_decode_split_chunk(); }
+
 // qkv [B T, (H + 2G) hd] contiguous; B, T, H, G, hd positive, H a multiple of G -> them as ints
 struct AttnDims { int B, T, H, G, hd; };
 AttnDims attn_args(const Op& op, const Tensor& qkv, int64_t B, int64_t T, int64_t H, int64_t G, int64_t hd) {
@@ -1279,7 +1334,7 @@ Tensor linear_residual(const Tensor& x, const Tensor& W, const Tensor& C) {
 // instrumented translation unit; always 0 in release builds (the checks are compiled away).
 int64_t debug_error() {
   const unsigned codes[] = {bllm::debug_take_embedding(), bllm::debug_take_loss(), bllm::debug_take_attn_decode(),
-                            bllm::debug_take_elementwise()};
+                            bllm::debug_take_attn_decode_split(), bllm::debug_take_elementwise()};
   for (unsigned c : codes)
     if (c) return (int64_t)c;
   return 0;
@@ -1301,6 +1356,7 @@ TORCH_LIBRARY(bllm, m) {
   m.def("debug_error() -> int", &debug_error);
   m.def("set_gemm_tile_maps(int wg_map, int wg_gm, int nt_map, int nt_gm) -> ()", &set_gemm_tile_maps);
   m.def("kernel_debug_build() -> bool", &kernel_debug_build);
+  m.def("attn_decode_split_chunk() -> int", &attn_decode_split_chunk);
   BLLM_OP("rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)", rmsnorm_fwd);
   BLLM_OP("rmsnorm_fwd_into_(Tensor x, Tensor w, float eps, Tensor(a!) y) -> Tensor", rmsnorm_fwd_into_);
   BLLM_OP("rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dx_acc, Tensor(a!)? dw_out, bool accumulate) -> (Tensor, Tensor)", rmsnorm_bwd);
@@ -1334,6 +1390,8 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("attn_decode(Tensor q, Tensor kcache, Tensor vcache, int L) -> Tensor", attn_decode);
   BLLM_OP("attn_decode_append(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append);
   BLLM_OP("attn_decode_append_rows(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_rows);
+  BLLM_OP("attn_decode_split(Tensor q, Tensor kcache, Tensor vcache, int L) -> Tensor", attn_decode_split);
+  BLLM_OP("attn_decode_append_split(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_split);
   BLLM_OP("kv_cache_fill_varlen(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) vcache) -> ()", kv_cache_fill_varlen);
   BLLM_OP("rope_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, int H, int G, int hd, Tensor pos) -> ()", rope_dev_);
   BLLM_OP("rope_pos_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos_ids, int H, int G, int hd, bool inverse) -> ()", rope_pos_);

@@ -11,7 +11,17 @@ synthetic Alpaca file in the ``--finetune`` prompt format, tokenised with the mo
 interleaved A B A B, ``--repeats`` times after one warm-up of each.  Per batch size one JSON line
 (and one entry of ``--out FILE``): median and range of ms per generated token (wall time over
 all B x tokens tokens) and responses/s.
-Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128"""
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128
+
+``--context N``: the model's context and the KV cache's length (the registry's Llama-3.1 / 3.2
+contexts go to 131,072).  ``generate_cached``, greedy, ``--batch`` rows of ``--prompt`` random
+tokens, ``--tokens`` new tokens, arms interleaved in one process ``--repeats`` times after one
+warm-up of each.  Up to 8,192 positions the arms are the single-launch decode-attention kernel
+and the split-KV kernels forced through ``ops.DECODE_SPLIT_MIN = 0``; past that the arms are
+graph replay (the append op: split-KV at every position of such a cache) and the eager loop (the
+plain op, which goes by the number of keys: single-launch up to 8,192 keys, split-KV beyond).  One JSON line: median and range
+of ms per generated token per arm (prefill included in the wall time, and reported on its own).
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 32768 --prompt 200"""
 import argparse
 import json
 import os
@@ -89,6 +99,46 @@ def ragged(a, m, cfg):
             json.dump(rows, f, indent=1)
 
 
+def context_bench(a, m, cfg):
+    ctx = cfg.context_length
+    if a.prompt + a.tokens > ctx:
+        sys.exit(f"bench_decode: prompt ({a.prompt}) + tokens ({a.tokens}) exceed --context ({ctx})")
+    idx = torch.randint(0, cfg.vocab_size, (a.batch, a.prompt), device="cuda")
+    default_min = ops.DECODE_SPLIT_MIN
+    if ctx <= default_min:
+        arms = {"single_launch": (default_min, "1"), "split": (0, "1")}
+    else:
+        arms = {"graph": (default_min, "1"), "eager": (default_min, "0")}
+
+    def run(arm, tokens):
+        ops.DECODE_SPLIT_MIN, os.environ["BLLM_DECODE_GRAPH"] = arms[arm]
+        try:
+            return G.generate_cached(m, idx, tokens, ctx)
+        finally:
+            ops.DECODE_SPLIT_MIN = default_min
+
+    outs = {k: run(k, a.tokens) for k in arms}         # warm-up of each arm
+    times = {k: [] for k in arms}
+    prefill = []
+    for _ in range(a.repeats):
+        for k in arms:
+            times[k].append(_timed(lambda: run(k, a.tokens)))
+        prefill.append(_timed(lambda: run(next(iter(arms)), 1)))
+    row = {"model": f"{a.model}-{a.num_params}", "context": ctx, "batch": a.batch, "prompt_tokens": a.prompt,
+           "new_tokens": a.tokens, "repeats": a.repeats,
+           "prefill_ms": round(1000 * statistics.median(prefill), 3)}
+    for k in arms:
+        ms = sorted(1000 * t / a.tokens for t in times[k])
+        row[k] = {"ms_per_token": round(statistics.median(ms), 4), "ms_per_token_range": [round(ms[0], 4), round(ms[-1], 4)]}
+    first, second = list(arms)
+    row["same_tokens"] = bool(torch.equal(outs[first], outs[second]))
+    print(json.dumps(row), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump([row], f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3")
@@ -99,10 +149,13 @@ def main():
     ap.add_argument("--graph", type=int, default=None, help="force the hipGraph decode step on/off")
     ap.add_argument("--ragged", default=None, help="comma list of batch sizes: generate_ragged vs one-row runs")
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=None, help="--ragged: also write the rows to this JSON file")
+    ap.add_argument("--out", default=None, help="--ragged / --context: also write the rows to this JSON file")
+    ap.add_argument("--context", type=int, default=None,
+                    help="model context = KV-cache length; compares the decode-attention kernels (see above)")
     a = ap.parse_args()
     ops.load_ext(required=True)
-    cfg = get_config(a.model, a.num_params).replace(dtype=torch.bfloat16)
+    cfg = (get_config(a.model, a.num_params) if a.context is None
+           else get_config(a.model, a.num_params, context_length=a.context)).replace(dtype=torch.bfloat16)
     torch.manual_seed(0)
     m = build_model(cfg, device="cuda")
     m.flatten()
@@ -110,6 +163,8 @@ def main():
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
     if a.ragged:
         return ragged(a, m, cfg)
+    if a.context is not None:
+        return context_bench(a, m, cfg)
     idx = torch.randint(0, cfg.vocab_size, (a.batch, a.prompt), device="cuda")
     g = torch.Generator(device="cuda").manual_seed(1)
     G.generate_cached(m, idx, 8, cfg.context_length, temperature=1.0, top_k=5, generator=g)  # warm-up
