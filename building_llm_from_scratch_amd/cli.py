@@ -39,6 +39,14 @@ def perform_checks(args):
             raise FileNotFoundError(f"--generate_prompts file '{args.generate_prompts}' does not exist.")
         if getattr(args, "generate_max_tokens", 256) < 1:
             raise ValueError("--generate_max_tokens must be at least 1.")
+    if not getattr(args, "generate_temperature", 0.0) >= 0.0:
+        raise ValueError("--generate_temperature must be >= 0 (0: greedy).")
+    if getattr(args, "generate_top_k", 0) < 0:
+        raise ValueError("--generate_top_k must be >= 0 (0: off).")
+    if not 0.0 < getattr(args, "generate_top_p", 1.0) <= 1.0:
+        raise ValueError("--generate_top_p must be in (0, 1] (1: off).")
+    if not -2 ** 63 <= getattr(args, "generate_seed", 0) < 2 ** 64:
+        raise ValueError("--generate_seed must fit 64 bits.")
     if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -153,11 +161,21 @@ def build_parser() -> argparse.ArgumentParser:
                         "schedule and every *_freq count optimizer steps")
     x.add_argument("--generate_prompts", type=str, default=None,
                    help="after training, answer the prompts of this JSON list in batches of --batch_size "
-                        "(train/generate.py:generate_ragged, greedy): an item is a string, used verbatim, or an "
+                        "(train/generate.py:generate_ragged; greedy unless --generate_temperature > 0): an item is "
+                        "a string, used verbatim, or an "
                         "Alpaca entry, prompted the way --finetune trains (its fields + '### Response:')")
     x.add_argument("--generate_out", type=str, default=None,
                    help="where rank 0 writes the [{prompt, response}] list (default <output_dir>/responses.json)")
     x.add_argument("--generate_max_tokens", type=int, default=256, help="new tokens per prompt at most")
+    x.add_argument("--generate_temperature", type=float, default=0.0,
+                   help="sampling temperature of --generate_prompts; 0: greedy.  Above 0 every prompt draws from its "
+                        "own seeded random stream on the device, so its answer does not depend on --batch_size "
+                        "or on the other prompts")
+    x.add_argument("--generate_top_k", type=int, default=0, help="keep the k largest logits (ties kept); 0: off")
+    x.add_argument("--generate_top_p", type=float, default=1.0,
+                   help="nucleus sampling after top-k: keep the largest logits that hold this share of the "
+                        "probability; 1: off")
+    x.add_argument("--generate_seed", type=int, default=0, help="seed of the sampled answers (--generate_temperature > 0)")
     x.add_argument("--generate_only", action="store_true",
                    help="no data preparation, training or final save: build the model (--load_weights / "
                         "--resume), answer --generate_prompts, exit")
@@ -239,7 +257,11 @@ def _generate_responses(trainer, args, rank, out_dir):
     rank 0 writes [{"prompt", "response"}] in input order, an entry's own fields kept."""
     import json
     items, texts = load_generate_prompts(args.generate_prompts)
-    responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size)
+    sampling = {}
+    if getattr(args, "generate_temperature", 0.0) > 0.0:
+        sampling = dict(temperature=args.generate_temperature, top_k=args.generate_top_k, top_p=args.generate_top_p,
+                        seed=args.generate_seed)
+    responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size, **sampling)
     if rank != 0:
         return
     rows = [{**(it if isinstance(it, dict) else {}), "prompt": t, "response": r}

@@ -26,7 +26,7 @@ __all__ = [
     "flash_attn_varlen_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
     "swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank_wgrad_ok",
     "gelu_fwd", "gelu_bwd", "gelu_bwd_bias", "gelu_bwd_act", "dropout_bwd_bias", "ce_fwd", "ce_bwd_", "embedding_fwd", "embedding_bwd",
-    "sq_norm_multi", "adamw_step_", "attn_decode", "attn_decode_append_rows", "kv_cache_fill_varlen", "bias_grad_", "ext_available", "load_ext", "attention_backend",
+    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "kv_cache_fill_varlen", "bias_grad_", "ext_available", "load_ext", "attention_backend",
     "lora_down", "lora_up_", "lora_wgrad", "lora_pack_t", "lora_kernel_ok", "lora_kernel_ok_dims",
     "lora_down_into", "lora_block_", "rmsnorm_fwd_into", "swiglu_fwd_into", "sum_partials_",
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
@@ -44,7 +44,8 @@ def _hip(t: torch.Tensor) -> bool:
 
 
 DEBUG_CODES = {1: "embedding token id outside [0, vocab)", 2: "cross-entropy target outside [0, V)",
-               3: "decode cache position outside [0, Tmax)", 4: "rope device position negative"}
+               3: "decode cache position outside [0, Tmax)", 4: "rope device position negative",
+               5: "sampler row counter outside [0, out.size(1))"}
 
 
 class _CheckedOps:
@@ -303,6 +304,28 @@ def attn_decode_append_rows(qkv, kc, vc, pos, H: int, G: int):
             return _k().attn_decode_append_split(qkv, kc, vc, pos, H, G)
         return _k().attn_decode_append_rows(qkv, kc, vc, pos, H, G)
     return ref.attn_decode_append_rows(qkv, kc, vc, pos, H, G)
+
+
+def sample_rows(logits, stream, ctr, seed: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                eos_id: int = -1, next_idx=None, out=None, finished=None, thr=None):
+    """One token per row of ``logits`` [B, V] (bf16 / fp16 / fp32) -> int64 [B]: temperature (0:
+    argmax, nothing else consulted), top-k (0 or >= V: off) and top-p (1: off) value thresholds,
+    then a Gumbel-max draw whose uniforms are a pure function of (seed, ``stream[b]``, ``ctr[b]``,
+    index) -- a row's token depends on nothing else in the call (``ops.reference.sample_rows_detail``
+    is the contract).  ``stream`` int64 [B], ``ctr`` int32 [B] = tokens the row has drawn so far.
+    In place, so that a decode step replays from a graph without host reads: the token also goes
+    to ``next_idx[b]`` (int64, B elements), ``out[b, ctr[b]]`` (int64 [B, n], unit column stride)
+    and, when it equals ``eos_id`` (negative: none), sets ``finished[b]`` (bool [B]); ``thr[b]``
+    (fp32 [B]) = the smallest kept logit, -inf when no filter is on; ``ctr[b] += 1``.  The caller
+    keeps every ``ctr[b] < out.shape[1]`` (the kernel clamps the column).  GPU tensors run the HIP
+    kernel (csrc/sample.hip), CPU tensors the oracle."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF          # any 64-bit seed, as the schema's signed int
+    seed -= (seed >> 63) << 64
+    if _hip(logits):
+        return _k().sample_rows(logits, stream, ctr, int(seed), float(temperature), int(top_k), float(top_p),
+                                int(eos_id), next_idx, out, finished, thr)
+    return ref.sample_rows(logits, stream, ctr, int(seed), float(temperature), int(top_k), float(top_p), int(eos_id),
+                           next_idx, out, finished, thr)
 
 
 def kv_cache_fill_varlen(qkv, cu, kc, vc):

@@ -61,6 +61,123 @@ def drop_keep_mask(seed: int, offset: int, numel: int, p: float, device=None) ->
 
 
 # ---------------------------------------------------------------------------
+# token sampler (identical bit-for-bit to csrc/common.h::sample_uniform; the contract of
+# csrc/sample.hip in fp64)
+# ---------------------------------------------------------------------------
+def _sample_row_keys(seed: int, stream: torch.Tensor, ctr: torch.Tensor):
+    """The two 32-bit row keys of (seed, stream[b], ctr[b]) as int64 tensors [B]."""
+    stream, ctr = stream.to(torch.int64), ctr.to(torch.int64)
+    seed &= 0xFFFFFFFFFFFFFFFF
+    words = [torch.full_like(stream, seed & _M32), torch.full_like(stream, seed >> 32),
+             stream & _M32, (stream >> 32) & _M32, ctr & _M32]
+    a, b = torch.full_like(stream, 0x9E3779B9), torch.full_like(stream, 0x85EBCA6B)
+    for w in words:
+        a = _mix32(a ^ w)
+        b = _mix32(b + w)
+    return a, b
+
+
+def sample_uniform(seed: int, stream: torch.Tensor, ctr: torch.Tensor, V: int) -> torch.Tensor:
+    """u[b, i] of the sampler's counter hash as fp64 [B, V]: an odd multiple of 2^-24, strictly
+    inside (0, 1) and exact in fp32."""
+    a, b = _sample_row_keys(seed, stream.reshape(-1), ctr.reshape(-1))
+    i = torch.arange(V, dtype=torch.int64, device=a.device)
+    h = _mix32(_mix32(i[None, :] ^ a[:, None]) + b[:, None])
+    return (((h >> 9) << 1) | 1).to(torch.float64) * 2.0 ** -24
+
+
+def sample_rows_detail(logits, stream, ctr, seed: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                       detail: bool = True):
+    """The sampler's contract in fp64 -> (tokens int64 [B], thr fp64 [B], details).
+
+    Row b: NaN logits count as -inf and +inf as the largest fp32; temperature 0 is the argmax
+    (lowest index on ties).  Otherwise top-k keeps ``l >= v_k`` (k-th largest value with
+    multiplicity, ties kept; 0 or >= V: off), then top-p keeps, inside that set, ``l >= v_p``:
+    the largest value whose upward mass ``sum{w_i : l_i >= v}``, ``w = exp((l - max) / T)``,
+    reaches ``top_p`` of the set's mass (1: off).  The token is the argmax over the kept set of
+    ``l / T - log(-log(u))`` (lowest index on ties), ``u = sample_uniform``.  ``thr`` is the
+    smallest kept value, -inf when no filter is on (and at temperature 0).  ``details[b]``
+    (``detail``): ``keys`` (fp64 [V], -inf outside the kept set), ``gap`` (top key minus the
+    runner-up; inf with one candidate), ``ratios`` (cumulative mass over the set's mass at the
+    end of every group of equal values, from the top; empty unless top-p is on) and ``kept``
+    (bool [V])."""
+    B, V = logits.shape
+    ninf = float("-inf")
+    l = torch.nan_to_num(logits.detach().to(torch.float64), nan=ninf, neginf=ninf,
+                         posinf=float(torch.finfo(torch.float32).max))
+    T = float(torch.tensor(float(temperature), dtype=torch.float32))   # the kernel's fp32 parameter
+    thr = torch.full((B,), ninf, dtype=torch.float64, device=l.device)
+
+    def first_max(x):                            # the lowest index of a row's maximum
+        return (x == x.max(dim=1, keepdim=True).values).to(torch.int8).argmax(dim=1)
+
+    if T == 0.0:
+        kept = torch.ones(B, V, dtype=torch.bool, device=l.device)
+        info = [{"keys": l[b], "gap": float("inf"), "ratios": l.new_zeros(0), "kept": kept[b]} for b in range(B)]
+        return first_max(l), thr, info if detail else None
+    live = l.max(dim=1).values > ninf            # a row of -inf only has nothing to filter
+    kept = torch.ones(B, V, dtype=torch.bool, device=l.device)
+    srt = gcum = None
+    if 0 < top_k < V:
+        vk = torch.where(live, torch.topk(l, top_k, dim=1).values[:, -1], thr)
+        kept = l >= vk[:, None]
+        thr = vk
+    if top_p < 1.0:
+        srt, order = torch.sort(l, dim=1, descending=True, stable=True)
+        mx = torch.where(live, srt[:, 0], torch.zeros_like(srt[:, 0]))
+        w = torch.where(kept.gather(1, order), torch.exp((srt - mx[:, None]) / T), torch.zeros_like(srt))
+        cum = w.cumsum(dim=1)
+        last = torch.ones(B, V, dtype=torch.bool, device=l.device)     # the end of a group of equal values
+        last[:, :-1] = srt[:, :-1] != srt[:, 1:]
+        # mass down to the end of each position's group: cum is non-decreasing, so that is the
+        # smallest group-end value at or after the position
+        gcum = torch.where(last, cum, torch.full_like(cum, float("inf"))).flip(1).cummin(dim=1).values.flip(1)
+        total = cum[:, -1:]
+        first = (gcum >= top_p * total).to(torch.int8).argmax(dim=1)
+        vp = torch.where(live, srt.gather(1, first[:, None])[:, 0], thr)
+        kept = kept & (l >= vp[:, None])
+        thr = vp
+    u = sample_uniform(seed, stream, ctr, V).to(l.device)
+    keys = torch.where(kept, l / T - torch.log(-torch.log(u)), torch.full_like(l, ninf))
+    tokens = first_max(keys)
+    if not detail:
+        return tokens, thr, None
+    info = []
+    for b in range(B):
+        top2 = torch.topk(keys[b], min(2, V)).values
+        gap = float(top2[0] - top2[1]) if V > 1 and int(kept[b].sum()) > 1 else float("inf")
+        ratios = l.new_zeros(0)
+        if gcum is not None and bool(live[b]):
+            ends = last[b] & (w[b] > 0)
+            ratios = cum[b][ends] / total[b]
+        info.append({"keys": keys[b], "gap": gap, "ratios": ratios, "kept": kept[b]})
+    return tokens, thr, info
+
+
+def sample_rows(logits, stream, ctr, seed: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                eos_id: int = -1, next_idx=None, out=None, finished=None, thr=None):
+    """``sample_rows_detail`` with the kernel's device-side state updates: the token goes to
+    ``next_idx[b]``, ``out[b, ctr[b]]`` (column clamped into out) and, when it equals
+    ``eos_id >= 0``, sets ``finished[b]``; ``thr[b]`` = smallest kept value (untouched at
+    temperature 0); ``ctr[b] += 1``."""
+    if top_k < 0 or not (0.0 < top_p <= 1.0) or not temperature >= 0.0:
+        raise ValueError(f"sample_rows: top_k {top_k} must be >= 0, top_p {top_p} in (0, 1], temperature "
+                         f"{temperature} >= 0")
+    tokens, t, _ = sample_rows_detail(logits, stream, ctr, seed, temperature, top_k, top_p, detail=False)
+    if next_idx is not None:
+        next_idx.view(-1).copy_(tokens)
+    if out is not None:
+        col = ctr.to(torch.int64).clamp(0, out.shape[1] - 1)
+        out[torch.arange(out.shape[0], device=out.device), col] = tokens
+    if finished is not None and eos_id >= 0:
+        finished |= tokens == eos_id
+    if thr is not None and float(temperature) > 0.0:
+        thr.copy_(t.to(thr.dtype))
+    ctr += 1
+    return tokens
+
+
+# ---------------------------------------------------------------------------
 # norms
 # ---------------------------------------------------------------------------
 def rmsnorm_fwd(x: torch.Tensor, w: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -25,6 +25,11 @@ Same contract: sliding window of ``context_size`` tokens, optional top-k thresho
   (``torch.cuda.CUDAGraph``) with the position kept in device memory, and replayed per token:
   one graph launch instead of ~12 kernel launches per layer (the decode loop is launch-bound
   below Llama-3-8B size).  ``BLLM_DECODE_GRAPH=0`` runs it eagerly.
+* ``seed=...`` switches :func:`generate_cached` / :func:`generate_ragged` from :func:`_sample`
+  (one ``torch.multinomial`` over the batch from one generator) to the device sampler
+  ``ops.sample_rows`` (csrc/sample.hip): temperature, top-k, top-p and a counter-based random
+  stream per row, so a row's tokens depend on (seed, its stream id, its logits) and not on the
+  batch it sits in.  In :func:`generate_ragged` the sampler is part of the captured step.
 """
 from __future__ import annotations
 
@@ -44,6 +49,29 @@ def _sample(logits, temperature, top_k, generator):
         probs = torch.softmax(logits / temperature, dim=-1)
         return torch.multinomial(probs, num_samples=1, generator=generator)
     return torch.argmax(logits, dim=-1, keepdim=True)
+
+
+def _sampler_args(fn: str, B: int, temperature, top_k, top_p, seed, streams):
+    """Entry check of the device sampler's arguments -> None (``seed is None``: :func:`_sample`
+    runs) or (top_k, top_p, stream ids) in the form ``ops.sample_rows`` takes."""
+    if seed is None:
+        if top_p is not None or streams is not None:
+            raise ValueError(f"{fn}: top_p and streams belong to the seeded device sampler; pass seed=...")
+        return None
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"{fn}: seed must be an int, got {seed!r}")
+    if not float(temperature) >= 0.0:
+        raise ValueError(f"{fn}: temperature must be >= 0, got {temperature}")
+    k = 0 if top_k is None else top_k
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"{fn}: top_k must be None or an int >= 0 (0: off), got {top_k!r}")
+    p = 1.0 if top_p is None else float(top_p)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"{fn}: top_p must be in (0, 1], got {top_p}")
+    ids = list(range(B)) if streams is None else [int(v) for v in streams]
+    if len(ids) != B or any(not -2 ** 63 <= v < 2 ** 63 for v in ids):
+        raise ValueError(f"{fn}: streams must hold one 64-bit stream id per row ({B}), got {len(ids)}")
+    return k, p, ids
 
 
 EOS_CHECK_EVERY = int(os.environ.get("BLLM_EOS_CHECK_EVERY", "16"))
@@ -89,7 +117,16 @@ class DecodeGraph:
 @torch.no_grad()
 def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, context_size: int, temperature: float = 0.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None,
-                    generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                    generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
+                    seed: Optional[int] = None, streams=None) -> torch.Tensor:
+    """``seed`` (with ``top_p``, ``streams``: row b's stream id, default b): tokens come from
+    ``ops.sample_rows`` instead of :func:`_sample`, called eagerly on each step's logits -- after
+    the graph replay, not inside it: this loop feeds the step from the host (``DecodeGraph.step``
+    copies the token and sets the position) and slides its window by re-prefilling.  Row b's
+    counter runs over all its tokens, re-prefills included, so no uniform is used twice.  The stop
+    rule and the sliding window are as without ``seed``."""
+    from .. import ops
+    sampler = _sampler_args("generate_cached", idx.shape[0], temperature, top_k, top_p, seed, streams)
     was_training = model.training
     model.eval()
     device = next(model.parameters()).device
@@ -98,6 +135,10 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, context_size:
     out = torch.empty(B, T0 + max(max_new_tokens, 0), dtype=idx.dtype, device=device)
     out[:, :T0] = idx
     n = checked = T0
+    if sampler is not None:
+        stream_t = torch.tensor(sampler[2], dtype=torch.long).to(device)
+        ctr = torch.zeros(B, dtype=torch.int32, device=device)    # row b has drawn ctr[b] tokens
+        new_cols = out[:, T0:]
     eng = model.rctx.engine
     resident = eng.params_resident() if hasattr(eng, "params_resident") else _null()
     with resident:
@@ -111,8 +152,12 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, context_size:
             logits = logits.clone()            # the prefill output must survive the capture
             dec = DecodeGraph(model, cache, B, device)
         for i in range(max_new_tokens):
-            idx_next = _sample(logits, temperature, top_k, generator)
-            out[:, n] = idx_next[:, 0]
+            if sampler is not None:            # writes column ctr = i of new_cols, i.e. out[:, n]
+                idx_next = ops.sample_rows(logits.contiguous(), stream_t, ctr, seed, temperature, sampler[0],
+                                           sampler[1], out=new_cols)[:, None]
+            else:
+                idx_next = _sample(logits, temperature, top_k, generator)
+                out[:, n] = idx_next[:, 0]
             n += 1
             last = i == max_new_tokens - 1
             if eos_id is not None and (n - checked >= EOS_CHECK_EVERY or last):
@@ -142,9 +187,14 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, context_size:
 class RowsDecodeGraph:
     """:class:`DecodeGraph` for ``forward_cached_rows``: the positions are an int32 [B] vector in
     device memory that the replayed step reads and :meth:`step` advances there.  Captured with
-    every position at the cache's last slot, as ``DecodeGraph`` does."""
+    every position at the cache's last slot, as ``DecodeGraph`` does.
 
-    def __init__(self, model, cache, pos: torch.Tensor, device):
+    ``sampler(logits, idx)`` (optional) is captured after the forward: it must pick the next token
+    of every row on the device and write it into ``idx`` (``ops.sample_rows`` with
+    ``next_idx=idx``); the position increment is captured too, so a token is one :meth:`replay`
+    and nothing else.  It is not called during the warm-up passes, whose logits mean nothing."""
+
+    def __init__(self, model, cache, pos: torch.Tensor, device, sampler=None):
         B, Tmax = pos.numel(), cache[0][0].shape[2]
         self.idx = torch.zeros(B, 1, dtype=torch.long, device=device)
         self.pos = torch.full((B,), Tmax - 1, dtype=torch.int32, device=device)
@@ -158,7 +208,14 @@ class RowsDecodeGraph:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.logits = model.forward_cached_rows(self.idx, cache, self.pos)
+            if sampler is not None:
+                sampler(self.logits, self.idx)
+                self.pos.add_(1)
         self.pos.copy_(pos)
+
+    def replay(self) -> None:
+        """One token of the forward + sampler graph: reads and rewrites ``idx``, advances ``pos``."""
+        self.graph.replay()
 
     def step(self, idx_next: torch.Tensor) -> torch.Tensor:
         self.idx.copy_(idx_next)
@@ -170,7 +227,8 @@ class RowsDecodeGraph:
 @torch.no_grad()
 def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temperature: float = 0.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None,
-                    generator: Optional[torch.Generator] = None) -> list:
+                    generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
+                    seed: Optional[int] = None, streams=None) -> list:
     """Batched KV-cache generation from prompts of different lengths.
 
     ``prompts``: a non-empty list of non-empty 1-D LongTensors.  Returns one 1-D tensor per prompt:
@@ -189,8 +247,18 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     eager), as in :func:`generate_cached`.
 
     Greedy (``temperature == 0``): row b is what ``generate_cached(model, prompts[b][None], ...)``
-    gives alone, up to GEMM rounding.  Sampling draws ONE multinomial over the [B, V]
-    probabilities per step, so a row's draws depend on which rows share its batch."""
+    gives alone, up to GEMM rounding.  Sampling without ``seed`` draws ONE multinomial over the
+    [B, V] probabilities per step, so a row's draws depend on which rows share its batch.
+
+    ``seed`` (an int) selects the device sampler ``ops.sample_rows`` instead: ``temperature``,
+    ``top_k`` (None / 0: off), ``top_p`` (None / 1: off; needs ``seed``) and one counter-based
+    random stream per row, ``streams[b]`` (default b), whose counter is the row's token count.
+    Row b's tokens are then a function of (seed, streams[b], row b's logits): the same prompt under
+    the same stream id gives the same answer in any batch, up to GEMM rounding of the logits.  The
+    first token is sampled eagerly from the prefill logits; after it the captured step is forward
+    + sampler, which writes the next input token, the output column and the finished mask on the
+    device, so the host loop is one graph replay per token (eager mode: the same two calls)."""
+    from .. import ops
     from ..models.base import pack_prompts
     if not isinstance(prompts, (list, tuple)) or len(prompts) == 0:
         raise ValueError("generate_ragged: prompts must be a non-empty list of 1-D token tensors")
@@ -205,6 +273,7 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     if context_size > model.cfg.context_length:
         raise ValueError(f"generate_ragged: context_size ({context_size}) exceeds the model's context length "
                          f"({model.cfg.context_length})")
+    sampler = _sampler_args("generate_ragged", len(prompts), temperature, top_k, top_p, seed, streams)
     device = next(model.parameters()).device
     if new == 0:
         return [p.to(device) for p in prompts]
@@ -222,10 +291,37 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
         cache = model.new_kv_cache(B, context_size)
         logits = model.forward_prefill_ragged(idx, seq, cache)
         dec = None
-        if new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
+        if sampler is not None:
+            stream_t = torch.tensor(sampler[2], dtype=torch.long).to(device)
+            ctr = torch.zeros(B, dtype=torch.int32, device=device)    # row b has drawn ctr[b] tokens
+            eos = -1 if eos_id is None else int(eos_id)
+
+            def draw(lg, nxt):     # token -> nxt, out[:, ctr], finished; ctr += 1 (ctr < new: one call per column)
+                return ops.sample_rows(lg.contiguous(), stream_t, ctr, seed, temperature, sampler[0], sampler[1],
+                                       eos_id=eos, next_idx=nxt, out=out, finished=finished)
+
+            nxt = torch.zeros(B, 1, dtype=torch.long, device=device)
+            draw(logits, nxt)
+            n = 1
+            if new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
+                dec = RowsDecodeGraph(model, cache, pos, device, sampler=draw)
+                dec.idx.copy_(nxt)
+            while n < new:
+                if eos_id is not None and n - checked >= EOS_CHECK_EVERY:
+                    if bool(finished.all()):   # tokens after a row's first eos are dropped below
+                        break
+                    checked = n
+                if dec is not None:
+                    dec.replay()
+                else:
+                    logits = model.forward_cached_rows(nxt, cache, pos)
+                    pos += 1
+                    draw(logits, nxt)
+                n += 1
+        elif new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
             logits = logits.clone()            # the prefill output must survive the capture
             dec = RowsDecodeGraph(model, cache, pos, device)
-        for i in range(new):
+        for i in range(new if sampler is None else 0):
             idx_next = _sample(logits, temperature, top_k, generator)
             out[:, i] = idx_next[:, 0]
             n = i + 1

@@ -495,9 +495,13 @@ class Trainer:
             logger.info(f"Generated Sample: {decoded.replace(chr(10), ' ')}")
         return decoded
 
-    def generate_responses(self, prompts, max_new_tokens: int, batch_size: int):
-        """Greedy continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in
-        input order, each cut before its first eos.  The prompts are sorted by token count and cut
+    def generate_responses(self, prompts, max_new_tokens: int, batch_size: int, temperature: float = 0.0,
+                           top_k=None, top_p=None, seed=None):
+        """Continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in input
+        order, each cut before its first eos: greedy by default; with ``seed`` sampled on the
+        device (``temperature``, ``top_k``, ``top_p``: :func:`generate_ragged`), prompt i drawing
+        from random stream i -- its index in ``prompts``, not its row in a sorted batch -- so an
+        answer does not change with ``batch_size`` or with the other prompts, up to GEMM rounding.  The prompts are sorted by token count and cut
         into batches of ``batch_size``, so a batch's rows have similar lengths, and every batch is
         one :func:`generate_ragged` call.  Every rank must call this with the same prompts (the
         engines gather parameters collectively, as for the sample print).  A prompt longer than
@@ -516,7 +520,10 @@ class Trainer:
         out = [None] * len(ids)
         for s in range(0, len(order), max(1, int(batch_size))):
             rows = order[s:s + max(1, int(batch_size))]
-            res = generate_ragged(self.model, [ids[i] for i in rows], max_new_tokens, ctx, eos_id=cfg["eos_id"])
+            sampling = {} if seed is None else dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                                    streams=rows)
+            res = generate_ragged(self.model, [ids[i] for i in rows], max_new_tokens, ctx, eos_id=cfg["eos_id"],
+                                  **sampling)
             for i, r in zip(rows, res):
                 out[i] = tok.decode(r[ids[i].numel():].tolist())
         return out

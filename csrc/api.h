@@ -14,6 +14,7 @@ unsigned int debug_take_loss();
 unsigned int debug_take_attn_decode();
 unsigned int debug_take_attn_decode_split();
 unsigned int debug_take_elementwise();
+unsigned int debug_take_sample();
 
 // norms.hip
 int norm_bwd_num_wg(int N, int d);
@@ -171,6 +172,16 @@ long embedding_bwd_part_floats(long N, int d);  // fp32 scratch the token backwa
 void embedding_bwd_tok(DType dt, const int64_t* sorted, const int64_t* perm, const void* dx, void* grad, float* part,
                        long N, int d, bool accumulate, hipStream_t s);
 void embedding_bwd_pos(DType dt, const void* dx, void* grad, int B, int T, int d, bool accumulate, hipStream_t s);
+
+// sample.hip — one token per row of logits [B, V]: temperature, top-k / top-p value thresholds and
+// a Gumbel-max draw from the counter-based stream (seed, stream[b], ctr[b]); temperature 0 is
+// argmax.  Device-side step state (each nullable but ctr): the token goes to tokens[b], next_idx[b],
+// out[b * out_ld + ctr[b]] (column clamped into [0, out_cols)) and, when == eos_id >= 0, sets
+// finished[b]; thr[b] = the smallest kept logit (-inf: nothing filtered; untouched at temperature
+// 0); ctr[b] += 1
+void sample_rows(DType dt, const void* logits, const int64_t* stream, int* ctr, uint64_t seed, float temperature,
+                 int top_k, double top_p, long eos_id, int64_t* next_idx, int64_t* out, long out_ld, int out_cols,
+                 unsigned char* finished, float* thr, int64_t* tokens, int B, int V, hipStream_t s);
 
 // lora.hip — see the file header for the operand conventions
 constexpr int LORA_MAX = 8;

@@ -13,6 +13,7 @@
 #include <torch/library.h>
 #include <hipblaslt/hipblaslt.h>
 
+#include <algorithm>
 #include <climits>
 #include <map>
 #include <mutex>
@@ -1329,12 +1330,55 @@ Tensor linear_residual(const Tensor& x, const Tensor& W, const Tensor& C) {
   return D;
 }
 
+// ------------------------------------------------------------------ sampler
+// logits [B, V] -> tokens int64 [B]: temperature (0: argmax), top-k (0 or >= V: off), top-p (1: off)
+// and a Gumbel-max draw from the counter-based stream (seed, stream[b], ctr[b]) (csrc/sample.hip).
+// Step state on the device, for graph replay: the token also goes to next_idx[b], out[b, ctr[b]]
+// and (== eos_id; negative: no eos) finished[b]; thr[b] = smallest kept logit; ctr[b] += 1.
+// ctr[b] < out.size(1) lives in device memory and cannot be checked here without a sync: the
+// generate functions guarantee it by construction (one call per output column), the kernel
+// clamps the column it writes, and the kernel-debug build reports a counter outside out.
+Tensor sample_rows(const Tensor& logits, const Tensor& streams, Tensor& ctr, int64_t seed, double temperature,
+                   int64_t top_k, double top_p, int64_t eos_id, const optional<Tensor>& next_idx,
+                   const optional<Tensor>& out, const optional<Tensor>& finished, const optional<Tensor>& thr) {
+  Op op("sample_rows", logits, "logits");
+  op.dense(logits, "logits");
+  op.dims(logits, 2, "logits");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B > 0 && V > 0, "sample_rows: logits must be a non-empty [B, V], got ", logits.sizes());
+  TORCH_CHECK(temperature >= 0.0, "sample_rows: temperature must be >= 0, got ", temperature);   // false for NaN
+  TORCH_CHECK(top_k >= 0, "sample_rows: top_k must be >= 0 (0: off), got ", top_k);
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_rows: top_p must be in (0, 1], got ", top_p);
+  op.vec(streams, B, at::kLong, "stream");
+  op.vec(ctr, B, at::kInt, "ctr");
+  const Tensor *ni = opt(next_idx), *o = opt(out), *fin = opt(finished), *th = opt(thr);
+  if (ni) op.vec(*ni, B, at::kLong, "next_idx");
+  if (o) {   // [B, n >= 1] rows with unit column stride (a column range of a wider buffer is fine)
+    op.on_gpu(*o, "out");
+    op.dtype(*o, at::kLong, "out");
+    TORCH_CHECK(o->dim() == 2 && o->size(0) == B && o->size(1) >= 1 && o->stride(1) == 1 &&
+                    (B == 1 || o->stride(0) >= o->size(1)),
+                "sample_rows: out must be [", B, ", >= 1] with unit column stride and rows that do not overlap, got ",
+                o->sizes(), " strides ", o->strides());
+  }
+  if (fin) op.vec(*fin, B, at::kBool, "finished");
+  if (th) op.vec(*th, B, at::kFloat, "thr");
+  auto tokens = at::empty({B}, logits.options().dtype(at::kLong));
+  bllm::sample_rows(dt_of(logits), logits.data_ptr(), streams.data_ptr<int64_t>(), ctr.data_ptr<int>(), (uint64_t)seed,
+                    (float)temperature, op.to_int(std::min<int64_t>(top_k, INT_MAX), "top_k"), top_p, (long)eos_id,
+                    opt_ptr<int64_t>(ni), opt_ptr<int64_t>(o), o ? (long)o->stride(0) : 0L,
+                    o ? op.to_int(o->size(1), "out columns") : 0, opt_ptr<unsigned char>(fin), opt_ptr<float>(th),
+                    tokens.data_ptr<int64_t>(), op.to_int(B, "B"), op.to_int(V, "V"), stream());
+  return tokens;
+}
+
 // ------------------------------------------------------------------ kernel debug mode
 // First failed device-side check since the last call (common.h DebugCode; 0 = none), over every
 // instrumented translation unit; always 0 in release builds (the checks are compiled away).
 int64_t debug_error() {
   const unsigned codes[] = {bllm::debug_take_embedding(), bllm::debug_take_loss(), bllm::debug_take_attn_decode(),
-                            bllm::debug_take_attn_decode_split(), bllm::debug_take_elementwise()};
+                            bllm::debug_take_attn_decode_split(), bllm::debug_take_elementwise(),
+                            bllm::debug_take_sample()};
   for (unsigned c : codes)
     if (c) return (int64_t)c;
   return 0;
@@ -1401,6 +1445,7 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("flash_attn_bwd(Tensor qkv, Tensor o, Tensor lse, Tensor dout, int B, int T, int H, int G, int hd, bool causal, float p, int seed, int offset, Tensor? keep_mask=None, Tensor? rope_cos=None, Tensor? rope_sin=None) -> Tensor", flash_attn_bwd);
   BLLM_OP("ce_fwd(Tensor logits, Tensor targets, int ignore_index) -> (Tensor, Tensor)", ce_fwd);
   BLLM_OP("ce_bwd_(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor scale, int ignore_index) -> ()", ce_bwd_);
+  BLLM_OP("sample_rows(Tensor logits, Tensor stream, Tensor(a!) ctr, int seed, float temperature, int top_k, float top_p, int eos_id, Tensor(b!)? next_idx, Tensor(c!)? out, Tensor(d!)? finished, Tensor(e!)? thr) -> Tensor", sample_rows);
   BLLM_OP("embedding_fwd(Tensor idx, Tensor wte, Tensor? wpe, int T, float p, int seed, int offset) -> Tensor", embedding_fwd);
   BLLM_OP("embedding_bwd(Tensor idx, Tensor dx, Tensor(a!)? grad_wte, Tensor(b!)? grad_wpe, int T, bool accumulate) -> ()", embedding_bwd);
   BLLM_OP("lora_down(Tensor x, Tensor[] ws, int[] c0, int[] lens, int[] ocol, int R, float scale) -> Tensor", lora_down);

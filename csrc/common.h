@@ -201,6 +201,29 @@ inline float drop_inv_keep(float p) {
   return t >= 65536u ? 0.f : (float)(65536.0 / (65536.0 - (double)t));
 }
 
+// ---------------------------------------------------------------- sampler RNG
+// Counter-based uniforms of the token sampler (csrc/sample.hip): u is a pure function of
+// (seed, stream, ctr, i) -- run seed, the row's stream id, the number of tokens the row has drawn,
+// the vocabulary index.  Two 32-bit row keys absorb (seed, stream, ctr) word by word; an element
+// then costs two mix32 (one round would make a row's uniforms an XOR-permutation of another
+// row's).  u is an odd multiple of 2^-24: strictly inside (0, 1) and exact in fp32.  Bit-identical
+// to ops/reference.py:sample_uniform.
+struct SampleKeys { uint32_t a, b; };
+__device__ __forceinline__ SampleKeys sample_row_keys(uint64_t seed, uint64_t stream, uint32_t ctr) {
+  const uint32_t w[5] = {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), ctr};
+  SampleKeys k = {0x9E3779B9u, 0x85EBCA6Bu};
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    k.a = mix32(k.a ^ w[j]);
+    k.b = mix32(k.b + w[j]);
+  }
+  return k;
+}
+__device__ __forceinline__ float sample_uniform(SampleKeys k, uint32_t i) {
+  const uint32_t h = mix32(mix32(i ^ k.a) + k.b);
+  return (float)(((h >> 9) << 1) | 1u) * 5.9604644775390625e-8f;   // (2m + 1) 2^-24, m < 2^23
+}
+
 // LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4) issued from inline asm so hipcc does
 // not track it: the compiler otherwise guards every later ds_read with s_waitcnt vmcnt(0)
 // (it cannot prove the in-flight DMA targets the other LDS buffer), which serialises the
@@ -286,6 +309,7 @@ enum DebugCode : unsigned int {
   DBG_CE_TARGET = 2,     // cross-entropy: target outside [0, V) and != ignore_index
   DBG_DECODE_POS = 3,    // decode: cache position outside [0, Tmax) or beyond the LDS score buffer
   DBG_ROPE_POS = 4,      // rope: device position negative
+  DBG_SAMPLE_CTR = 5,    // sampler: row counter outside [0, out.size(1))
 };
 #ifdef BLLM_KERNEL_DEBUG
 #define BLLM_DEBUG_WORD(tu)                                                                        \

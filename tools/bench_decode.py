@@ -13,6 +13,12 @@ interleaved A B A B, ``--repeats`` times after one warm-up of each.  Per batch s
 all B x tokens tokens) and responses/s.
 Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128
 
+``--ragged ... --temperature T [--top_k K] [--top_p P] [--seed S]``: what sampling costs.  Three
+``generate_ragged`` arms over the same prompts, interleaved in one process: greedy, the torch
+composition (``_sample``: topk / softmax / multinomial from one generator after each replay; left
+out when ``--top_p`` < 1, which it cannot do) and the device sampler (``seed=S``: csrc/sample.hip
+inside the replayed step).  Median and range of ms per generated token per arm.
+
 ``--context N``: the model's context and the KV cache's length (the registry's Llama-3.1 / 3.2
 contexts go to 131,072).  ``generate_cached``, greedy, ``--batch`` rows of ``--prompt`` random
 tokens, ``--tokens`` new tokens, arms interleaved in one process ``--repeats`` times after one
@@ -99,6 +105,41 @@ def ragged(a, m, cfg):
             json.dump(rows, f, indent=1)
 
 
+def ragged_sampling(a, m, cfg):
+    sizes = [int(b) for b in a.ragged.split(",")]
+    prompts, tok_name = _alpaca_prompts(a.model, cfg, max(sizes))
+    ctx = cfg.context_length
+    top_k = a.top_k if a.top_k > 0 else None
+    rows = []
+    for B in sizes:
+        ps = prompts[:B]
+        gen = torch.Generator(device="cuda").manual_seed(a.seed)
+        arms = {"greedy": lambda: G.generate_ragged(m, ps, a.tokens, ctx)}
+        if a.top_p >= 1.0:
+            arms["torch_sample"] = lambda: G.generate_ragged(m, ps, a.tokens, ctx, temperature=a.temperature,
+                                                             top_k=top_k, generator=gen)
+        arms["device_sample"] = lambda: G.generate_ragged(m, ps, a.tokens, ctx, temperature=a.temperature, top_k=top_k,
+                                                          top_p=a.top_p, seed=a.seed)
+        for fn in arms.values():
+            fn()
+        times = {k: [] for k in arms}
+        for _ in range(a.repeats):
+            for k, fn in arms.items():
+                times[k].append(_timed(fn))
+        row = {"model": f"{a.model}-{a.num_params}", "batch": B, "new_tokens": a.tokens, "repeats": a.repeats,
+               "tokenizer": tok_name, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
+               "graph": os.environ.get("BLLM_DECODE_GRAPH", "default")}
+        for k in arms:
+            st = _stats(times[k], B, a.tokens)
+            row[k] = {"ms_per_token": st["ms_per_token"], "ms_per_token_range": st["ms_per_token_range"]}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def context_bench(a, m, cfg):
     ctx = cfg.context_length
     if a.prompt + a.tokens > ctx:
@@ -150,6 +191,10 @@ def main():
     ap.add_argument("--ragged", default=None, help="comma list of batch sizes: generate_ragged vs one-row runs")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None, help="--ragged / --context: also write the rows to this JSON file")
+    ap.add_argument("--temperature", type=float, default=0.0, help="--ragged: > 0 compares the sampling paths (see above)")
+    ap.add_argument("--top_k", type=int, default=0)
+    ap.add_argument("--top_p", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--context", type=int, default=None,
                     help="model context = KV-cache length; compares the decode-attention kernels (see above)")
     a = ap.parse_args()
@@ -162,7 +207,7 @@ def main():
     if a.graph is not None:
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
     if a.ragged:
-        return ragged(a, m, cfg)
+        return ragged_sampling(a, m, cfg) if a.temperature > 0 else ragged(a, m, cfg)
     if a.context is not None:
         return context_bench(a, m, cfg)
     idx = torch.randint(0, cfg.vocab_size, (a.batch, a.prompt), device="cuda")
