@@ -47,6 +47,8 @@ def perform_checks(args):
         raise ValueError("--generate_top_p must be in (0, 1] (1: off).")
     if not -2 ** 63 <= getattr(args, "generate_seed", 0) < 2 ** 64:
         raise ValueError("--generate_seed must fit 64 bits.")
+    if getattr(args, "generate_kv_dtype", "model") not in ("model", "fp8"):
+        raise ValueError("--generate_kv_dtype must be 'model' or 'fp8'.")
     if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -176,6 +178,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="nucleus sampling after top-k: keep the largest logits that hold this share of the "
                         "probability; 1: off")
     x.add_argument("--generate_seed", type=int, default=0, help="seed of the sampled answers (--generate_temperature > 0)")
+    x.add_argument("--generate_kv_dtype", type=str, default="model",
+                   help="KV cache of --generate_prompts: 'model' keeps it in the parameter dtype; 'fp8' stores e4m3 bytes "
+                        "with one fp32 scale per (row, kv head, position), about half the bytes (answers can differ)")
     x.add_argument("--generate_only", action="store_true",
                    help="no data preparation, training or final save: build the model (--load_weights / "
                         "--resume), answer --generate_prompts, exit")
@@ -261,6 +266,8 @@ def _generate_responses(trainer, args, rank, out_dir):
     if getattr(args, "generate_temperature", 0.0) > 0.0:
         sampling = dict(temperature=args.generate_temperature, top_k=args.generate_top_k, top_p=args.generate_top_p,
                         seed=args.generate_seed)
+    if getattr(args, "generate_kv_dtype", "model") == "fp8":
+        sampling["kv_dtype"] = "fp8"
     responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size, **sampling)
     if rank != 0:
         return

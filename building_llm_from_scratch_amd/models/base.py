@@ -230,6 +230,14 @@ class UnitCompute:
         raise NotImplementedError
 
 
+def _no_fp8_cache(kv, what: str) -> None:
+    """The fixed-position paths keep the cache in the activation dtype: an fp8 cache
+    (``new_kv_cache(..., kv_dtype="fp8")``) belongs to the per-row path only."""
+    if len(kv) != 2 or kv[0].dtype == torch.float8_e4m3fn:
+        raise ValueError(f"{what} does not take an fp8 KV cache: use generate_ragged (forward_prefill_ragged / "
+                         f"forward_cached_rows)")
+
+
 def cached_attention(qkv, B: int, t: int, pos: int, H: int, G: int, hd: int, kv, causal: bool = True):
     """Attention of ``t`` new tokens at positions ``pos..pos+t-1`` (packed qkv rows, RoPE
     already applied) against a per-block KV cache ``kv = (k, v)`` of [B, G, Tmax, hd]; the new
@@ -237,6 +245,7 @@ def cached_attention(qkv, B: int, t: int, pos: int, H: int, G: int, hd: int, kv,
     on the packed rows; single-token decode runs the HIP decode kernel over the cache (past
     ``ops.DECODE_SPLIT_MIN`` keys the split-KV one, so the cache may be as long as the context)."""
     from .. import ops
+    _no_fp8_cache(kv, "cached_attention")
     kc, vc = kv
     rows = qkv.view(B, t, H + 2 * G, hd)
     kc[:, :, pos:pos + t].copy_(rows[:, :, H:H + G].transpose(1, 2))
@@ -562,13 +571,25 @@ class BaseLM(nn.Module):
             return logits.view(B, T, -1)
 
     # -- KV-cache inference -------------------------------------------------------------
-    def new_kv_cache(self, B: int, max_len: int):
-        """Per-block (K, V) caches [B, G, max_len, hd] in the parameter dtype."""
+    def new_kv_cache(self, B: int, max_len: int, kv_dtype: Optional[str] = None):
+        """Per-block (K, V) caches [B, G, max_len, hd] in the parameter dtype.  ``kv_dtype="fp8"``:
+        per block (K8, V8, Ks, Vs), e4m3fn bytes [B, G, max_len, hd] and one fp32 scale per (row, kv
+        head, position) [B, G, max_len] (``ops.kv_quantize_rows`` is the format): (hd + 4) / (2 hd)
+        of the bf16 bytes, for the per-row path (``forward_prefill_ragged`` / ``forward_cached_rows``)."""
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"new_kv_cache: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
         self._ensure_flat()
         cfg = self.cfg
         G = cfg.n_kv_groups if cfg.is_llama else cfg.n_heads
         p = self._comps[1].unit
         dev, dt = self._anchor.device, (p.train.dtype if p.train is not None else p.frozen.dtype)
+        if kv_dtype == "fp8":
+            def bytes_():
+                return torch.empty(B, G, max_len, cfg.head_dim, device=dev, dtype=torch.float8_e4m3fn)
+
+            def scales_():
+                return torch.empty(B, G, max_len, device=dev, dtype=torch.float32)
+            return [(bytes_(), bytes_(), scales_(), scales_()) for _ in range(len(self._comps) - 2)]
         return [(torch.empty(B, G, max_len, cfg.head_dim, device=dev, dtype=dt),
                  torch.empty(B, G, max_len, cfg.head_dim, device=dev, dtype=dt))
                 for _ in range(len(self._comps) - 2)]
@@ -580,6 +601,7 @@ class BaseLM(nn.Module):
         ``engine.params_resident()`` (FSDP) — see train/generate.py:generate_cached."""
         self._ensure_flat()
         comps, rc = self._comps, self._rctx
+        _no_fp8_cache(cache[0], "forward_cached")
         rc.sync_all_params()
         B, t = idx.shape
         idx = idx.to(self._anchor.device)
@@ -591,10 +613,14 @@ class BaseLM(nn.Module):
     def decode_graph_ok(self, cache) -> bool:
         """Whether :meth:`forward_cached_dev` runs on this model / cache (GPU, bf16/fp16, head
         dim 64/128; any cache length: past ``ops.DECODE_SPLIT_MIN`` positions the split-KV
-        decode kernel takes over)."""
+        decode kernel takes over).  An fp8 cache (:meth:`forward_cached_rows` only) under the same
+        conditions on the activations, which are in the parameter dtype."""
         dev = self._anchor.device if self._anchor is not None else torch.device("cpu")
-        kc = cache[0][0]
-        return (dev.type == "cuda" and kc.dtype in (torch.bfloat16, torch.float16)
+        dt = cache[0][0].dtype
+        if dt == torch.float8_e4m3fn:
+            p = self._comps[1].unit
+            dt = p.train.dtype if p.train is not None else p.frozen.dtype
+        return (dev.type == "cuda" and dt in (torch.bfloat16, torch.float16)
                 and self.cfg.head_dim in (64, 128))
 
     @torch.no_grad()
@@ -603,6 +629,7 @@ class BaseLM(nn.Module):
         device): no host-side position, no host sync, so the whole step can be captured in a HIP
         graph once and replayed per token (train/generate.py)."""
         comps = self._comps
+        _no_fp8_cache(cache[0], "forward_cached_dev")
         x = comps[0].infer_dev(idx, pos_t)
         for c, kv in zip(comps[1:-1], cache):
             x = c.infer_dev(x, pos_t, kv)

@@ -186,7 +186,7 @@ class GPTBlockCompute(UnitCompute):
         """``infer_dev`` with a position per row (int32 [B] on the device)."""
         H = self.rctx.cfg.n_heads
         qkv, _ = self.qkv.forward(self._ln(x2d, self.block.norm1)[0])
-        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, H))
+        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, H, scales=kv[2:]))
 
     def infer_ragged(self, x2d, seq, kv):
         """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,
@@ -195,7 +195,7 @@ class GPTBlockCompute(UnitCompute):
         H, hd = cfg.n_heads, cfg.head_dim
         qkv, _ = self.qkv.forward(self._ln(x2d, self.block.norm1)[0])
         o, _ = ops.flash_attn_varlen_fwd(qkv, seq.cu, seq.max_len, H, H, hd, bounds=seq.bounds)
-        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1])
+        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1], scales=kv[2:])
         return self._infer_out(x2d, o)
 
     def infer(self, x2d, B, t, pos, kv):

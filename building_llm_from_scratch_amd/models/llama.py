@@ -289,7 +289,7 @@ class LlamaBlockCompute(UnitCompute):
         cos, sin = self.rctx.rope
         qkv = self._infer_qkv(x2d)
         ops.rope_pos_(qkv, cos, sin, pos_rows, H, G, hd)
-        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G))
+        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G, scales=kv[2:]))
 
     def infer_ragged(self, x2d, seq, kv):
         """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,
@@ -300,7 +300,7 @@ class LlamaBlockCompute(UnitCompute):
         qkv = self._infer_qkv(x2d)
         ops.rope_pos_(qkv, cos, sin, seq.pos_ids, H, G, hd)
         o, _ = ops.flash_attn_varlen_fwd(qkv, seq.cu, seq.max_len, H, G, hd, bounds=seq.bounds)
-        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1])
+        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1], scales=kv[2:])
         return self._infer_out(x2d, o)
 
     def infer(self, x2d, B, t, pos, kv):

@@ -26,7 +26,7 @@ __all__ = [
     "flash_attn_varlen_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
     "swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank_wgrad_ok",
     "gelu_fwd", "gelu_bwd", "gelu_bwd_bias", "gelu_bwd_act", "dropout_bwd_bias", "ce_fwd", "ce_bwd_", "embedding_fwd", "embedding_bwd",
-    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "kv_cache_fill_varlen", "bias_grad_", "ext_available", "load_ext", "attention_backend",
+    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "kv_cache_fill_varlen", "kv_quantize_rows", "kv_dequantize", "bias_grad_", "ext_available", "load_ext", "attention_backend",
     "lora_down", "lora_up_", "lora_wgrad", "lora_pack_t", "lora_kernel_ok", "lora_kernel_ok_dims",
     "lora_down_into", "lora_block_", "rmsnorm_fwd_into", "swiglu_fwd_into", "sum_partials_",
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
@@ -292,12 +292,45 @@ def _decode_kernel(t, hd: int) -> bool:
     return t.device.type == "cuda" and t.dtype in (torch.bfloat16, torch.float16) and hd in (64, 128)
 
 
-def attn_decode_append_rows(qkv, kc, vc, pos, H: int, G: int):
+kv_quantize_rows = ref.kv_quantize_rows
+kv_dequantize = ref.kv_dequantize
+
+
+def _fp8_scales(name: str, kc, vc, scales):
+    """The (Ks, Vs) of an fp8 cache, or None for a cache in the activation dtype.  ``scales`` is
+    what follows (K, V) in a block's cache tuple: empty / None, or the two fp32 scale tensors
+    [B, G, Tmax] of e4m3fn caches (``ops.reference.kv_quantize_rows`` is the format)."""
+    fp8 = kc.dtype == torch.float8_e4m3fn
+    if not scales:
+        if fp8 or vc.dtype == torch.float8_e4m3fn:
+            raise ValueError(f"{name}: an fp8 cache needs scales=(Ks, Vs)")
+        return None
+    if len(scales) != 2 or not fp8 or vc.dtype != kc.dtype:
+        raise ValueError(f"{name}: scales=(Ks, Vs) go with float8_e4m3fn K and V caches, got {kc.dtype} / {vc.dtype}")
+    for t in scales:
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(kc.shape[:3]):
+            raise ValueError(f"{name}: cache scales must be fp32 {tuple(kc.shape[:3])}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    return scales[0], scales[1]
+
+
+def attn_decode_append_rows(qkv, kc, vc, pos, H: int, G: int, scales=None):
     """``attn_decode_append`` with a position per batch row (``pos`` int32 [B] on qkv's device):
     row b appends its K/V at cache row ``pos[b]`` and attends over keys 0..pos[b].  bf16 / fp16
     with head dim 64 / 128 run the HIP kernel (no host read: graph-capturable; caches of more than
     ``DECODE_SPLIT_MIN`` positions the split-KV one); CPU tensors, fp32 and other head dims go to
-    the oracle, as in ``attn_decode``."""
+    the oracle, as in ``attn_decode``.
+
+    ``scales=(Ks, Vs)``: ``kc`` / ``vc`` are an fp8 cache (e4m3fn bytes, one fp32 scale per row,
+    kv head and position).  The new k / v are quantised into row ``pos[b]`` and the step attends
+    over the dequantised cache, the new key included: the split-KV fp8 kernel
+    (csrc/attn_decode_fp8.hip) at every cache length, the oracle where the plain cache takes it."""
+    sc = _fp8_scales("attn_decode_append_rows", kc, vc, scales)
+    if sc is not None:
+        if _decode_kernel(qkv, kc.shape[3]):
+            load_ext(required=True)
+            return _k().attn_decode_append_rows_fp8(qkv, kc, sc[0], vc, sc[1], pos, H, G)
+        return ref.attn_decode_append_rows_fp8(qkv, kc, vc, sc[0], sc[1], pos, H, G)
     if _decode_kernel(qkv, kc.shape[3]):
         load_ext(required=True)
         if kc.shape[2] > DECODE_SPLIT_MIN:
@@ -328,12 +361,23 @@ def sample_rows(logits, stream, ctr, seed: int, temperature: float, top_k: int =
                            next_idx, out, finished, thr)
 
 
-def kv_cache_fill_varlen(qkv, cu, kc, vc):
+def kv_cache_fill_varlen(qkv, cu, kc, vc, scales=None):
     """Fill the caches [B, G, Tmax, hd] from a packed batch: sequence b is rows [cu[b], cu[b+1]) of
     qkv [N, (H+2G)*hd] (``cu`` int32 [B + 1] on qkv's device, every length <= Tmax -- the caller
     checks its host bounds); cache rows (b, g, t < len_b) get the K/V of row cu[b] + t, every
     other cache element stays.  One launch for bf16 / fp16 / fp32 (head rows of whole 16-byte
-    vectors; any other head dim goes to the oracle)."""
+    vectors; any other head dim goes to the oracle).
+
+    ``scales=(Ks, Vs)``: an fp8 cache (see ``attn_decode_append_rows``); the rows are quantised on
+    the way in and their scales written, in one launch for bf16 / fp16 with head dim 64 / 128."""
+    sc = _fp8_scales("kv_cache_fill_varlen", kc, vc, scales)
+    if sc is not None:
+        if _decode_kernel(qkv, kc.shape[3]):
+            load_ext(required=True)
+            _k().kv_cache_fill_varlen_fp8(qkv, cu, kc, sc[0], vc, sc[1])
+            return
+        ref.kv_cache_fill_varlen_fp8(qkv, cu, kc, vc, sc[0], sc[1])
+        return
     if qkv.device.type == "cuda" and (kc.shape[3] * kc.element_size()) % 16 == 0:
         load_ext(required=True)
         _k().kv_cache_fill_varlen(qkv, cu, kc, vc)

@@ -565,6 +565,61 @@ def kv_cache_fill_varlen(qkv, cu, kcache, vcache):
         vcache[b, :, :r1 - r0] = rows[r0:r1, H + G:].transpose(0, 1)
 
 
+# ------------------------------------------------------------------ FP8 KV cache (csrc/attn_decode_fp8.hip oracle)
+# The format: a head row x (its last dimension, read as fp32) is stored as e4m3fn bytes and one
+# fp32 scale.  a = max |x|; s = a / 448, or 1 when a = 0; byte_i = e4m3fn_rne(x_i / s); both
+# divisions are correctly rounded fp32 divisions (formed here in fp64 and rounded once: the fp64
+# quotient of two fp32 numbers is far enough from every fp32 rounding boundary that the second
+# rounding changes nothing).  |x_i / s| <= 448 (1 + 2^-23), which the cast rounds to 448, so it
+# never saturates.  Dequantised value = float(byte_i) * s.  A block's fp8 cache is
+# (K8, V8, Ks, Vs): bytes [B, G, Tmax, hd] and scales [B, G, Tmax].
+FP8_MAX = 448.0
+
+
+def kv_quantize_rows(x):
+    """x [..., hd] (bf16 / fp16 / fp32) -> (bytes [..., hd] float8_e4m3fn, scales [...] fp32)."""
+    x64 = x.float().double()
+    a = x64.abs().amax(dim=-1)
+    s = torch.where(a > 0, a / FP8_MAX, torch.ones_like(a)).float()
+    q = (x64 / s.double()[..., None]).float().to(torch.float8_e4m3fn)
+    return q, s
+
+
+def kv_dequantize(q, s, dtype=torch.float32):
+    """bytes [..., hd] float8_e4m3fn and scales [...] fp32 -> [..., hd] of ``dtype`` (exact in fp32)."""
+    return (q.float() * s[..., None]).to(dtype)
+
+
+def attn_decode_append_rows_fp8(qkv, k8, v8, kscale, vscale, pos, H: int, G: int):
+    """``attn_decode_append_rows`` on an fp8 cache: row b's new k / v are quantised into cache row
+    pos[b] (bytes and scales), and its query attends over the dequantised keys 0..pos[b], the new
+    one included in its quantised form: a function of the cache contents after the append."""
+    B, hd = qkv.shape[0], k8.shape[3]
+    rows = qkv.view(B, H + 2 * G, hd)
+    out = torch.empty(B, H * hd, dtype=qkv.dtype, device=qkv.device)
+    for b, p in enumerate(int(p) for p in pos.tolist()):
+        k8[b, :, p], kscale[b, :, p] = kv_quantize_rows(rows[b, H:H + G])
+        v8[b, :, p], vscale[b, :, p] = kv_quantize_rows(rows[b, H + G:])
+        kd = kv_dequantize(k8[b:b + 1, :, :p + 1], kscale[b:b + 1, :, :p + 1])
+        vd = kv_dequantize(v8[b:b + 1, :, :p + 1], vscale[b:b + 1, :, :p + 1])
+        out[b] = attn_decode(rows[b:b + 1, :H], kd, vd, p + 1)[0]
+    return out
+
+
+def kv_cache_fill_varlen_fp8(qkv, cu, k8, v8, kscale, vscale):
+    """``kv_cache_fill_varlen`` into an fp8 cache: rows (b, g, t < len_b) and their scales <- the
+    quantised k / v of packed row cu[b] + t; nothing else is written."""
+    G, hd = k8.shape[1], k8.shape[3]
+    rows = qkv.view(qkv.shape[0], -1, hd)
+    H = rows.shape[1] - 2 * G
+    cb = varlen_bounds(cu)
+    for b, (r0, r1) in enumerate(zip(cb[:-1], cb[1:])):
+        for c8, cs, src in ((k8, kscale, rows[r0:r1, H:H + G]), (v8, vscale, rows[r0:r1, H + G:])):
+            q, s = kv_quantize_rows(src.transpose(0, 1))
+            c8[b, :, :r1 - r0] = q
+            cs[b, :, :r1 - r0] = s
+
+
 # ------------------------------------------------------------------ LoRA (csrc/lora.hip oracle)
 def lora_down(x, ws, c0, lens, ocol, R: int, scale: float = 1.0):
     """out[:, ocol_i : ocol_i + r_i] = scale * x[:, c0_i : c0_i + len_i] @ w_i[:, :len_i]^T"""

@@ -228,7 +228,7 @@ class RowsDecodeGraph:
 def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temperature: float = 0.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
-                    seed: Optional[int] = None, streams=None) -> list:
+                    seed: Optional[int] = None, streams=None, kv_dtype: Optional[str] = None) -> list:
     """Batched KV-cache generation from prompts of different lengths.
 
     ``prompts``: a non-empty list of non-empty 1-D LongTensors.  Returns one 1-D tensor per prompt:
@@ -257,9 +257,17 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     the same stream id gives the same answer in any batch, up to GEMM rounding of the logits.  The
     first token is sampled eagerly from the prefill logits; after it the captured step is forward
     + sampler, which writes the next input token, the output column and the finished mask on the
-    device, so the host loop is one graph replay per token (eager mode: the same two calls)."""
+    device, so the host loop is one graph replay per token (eager mode: the same two calls).
+
+    ``kv_dtype="fp8"`` keeps the KV cache as e4m3fn bytes with one fp32 scale per (row, kv head,
+    position) (``model.new_kv_cache``): about half the cache bytes.  The prefill attention still
+    runs on the exact K / V of the packed rows; what is stored, and what every later step attends
+    over, is quantised, so the tokens can differ from the default cache's.  None: the cache in the
+    parameter dtype, as before."""
     from .. import ops
     from ..models.base import pack_prompts
+    if kv_dtype not in (None, "fp8"):
+        raise ValueError(f"generate_ragged: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
     if not isinstance(prompts, (list, tuple)) or len(prompts) == 0:
         raise ValueError("generate_ragged: prompts must be a non-empty list of 1-D token tensors")
     for b, p in enumerate(prompts):
@@ -288,7 +296,8 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     eng = model.rctx.engine
     resident = eng.params_resident() if hasattr(eng, "params_resident") else _null()
     with resident:
-        cache = model.new_kv_cache(B, context_size)
+        cache = model.new_kv_cache(B, context_size) if kv_dtype is None else \
+            model.new_kv_cache(B, context_size, kv_dtype=kv_dtype)
         logits = model.forward_prefill_ragged(idx, seq, cache)
         dec = None
         if sampler is not None:

@@ -496,7 +496,7 @@ class Trainer:
         return decoded
 
     def generate_responses(self, prompts, max_new_tokens: int, batch_size: int, temperature: float = 0.0,
-                           top_k=None, top_p=None, seed=None):
+                           top_k=None, top_p=None, seed=None, kv_dtype=None):
         """Continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in input
         order, each cut before its first eos: greedy by default; with ``seed`` sampled on the
         device (``temperature``, ``top_k``, ``top_p``: :func:`generate_ragged`), prompt i drawing
@@ -506,7 +506,7 @@ class Trainer:
         one :func:`generate_ragged` call.  Every rank must call this with the same prompts (the
         engines gather parameters collectively, as for the sample print).  A prompt longer than
         ``context_length - max_new_tokens`` raises ValueError naming its index, before any
-        generation."""
+        generation.  ``kv_dtype="fp8"``: the quantised KV cache of :func:`generate_ragged`."""
         tok, cfg = self.loaderObj.tokenizer, self.config
         ctx = cfg["context_length"]
         ids = [text_to_token_ids(t, tok, cfg)[0] for t in prompts]
@@ -522,6 +522,8 @@ class Trainer:
             rows = order[s:s + max(1, int(batch_size))]
             sampling = {} if seed is None else dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                                     streams=rows)
+            if kv_dtype is not None:
+                sampling["kv_dtype"] = kv_dtype
             res = generate_ragged(self.model, [ids[i] for i in rows], max_new_tokens, ctx, eos_id=cfg["eos_id"],
                                   **sampling)
             for i, r in zip(rows, res):

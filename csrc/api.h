@@ -13,6 +13,7 @@ unsigned int debug_take_embedding();
 unsigned int debug_take_loss();
 unsigned int debug_take_attn_decode();
 unsigned int debug_take_attn_decode_split();
+unsigned int debug_take_attn_decode_fp8();
 unsigned int debug_take_elementwise();
 unsigned int debug_take_sample();
 
@@ -158,6 +159,18 @@ void attn_decode_split(DType dt, const void* q, const void* kc, const void* vc, 
                        int G, int hd, int Tmax, int L, hipStream_t s);
 void attn_decode_append_split(DType dt, const void* qkv, void* kc, void* vc, void* out, float* ws, const int* pos,
                               int pos_stride, int B, int H, int G, int hd, int Tmax, hipStream_t s);
+// the merge launch alone (a position per row), for a partial pass that wrote ws in the same layout
+void attn_decode_split_combine_rows(DType dt, const float* ws, void* out, const int* pos, int B, int H, int hd,
+                                    int Tmax, hipStream_t s);
+
+// attn_decode_fp8.hip -- the KV cache as e4m3fn bytes k8 / v8 [B, G, Tmax, hd] with one fp32 scale per
+// (row, kv head, position) ks / vs [B, G, Tmax]; dt is the dtype of qkv and out (bf16 / fp16), hd 64 / 128.
+// fill: kv_cache_fill_varlen, quantising.  decode: per-row append + attention in split-KV form for
+// any Tmax (ws and the grid limits of attn_decode_split.hip), two launches.
+void kv_cache_fill_varlen_fp8(DType dt, const void* qkv, const int* cu, void* k8, float* ks, void* v8, float* vs,
+                              long N, int B, int H, int G, int hd, int Tmax, hipStream_t s);
+void attn_decode_append_rows_fp8(DType dt, const void* qkv, void* k8, float* ks, void* v8, float* vs, void* out,
+                                 float* ws, const int* pos, int B, int H, int G, int hd, int Tmax, hipStream_t s);
 
 // loss.hip
 void ce_fwd(DType dt, const void* logits, const int64_t* tgt, float* loss, float* lse, long N, long V, long ld,

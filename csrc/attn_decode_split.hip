@@ -25,13 +25,11 @@
 // either launch reads: key L - 1 is taken from the qkv row).  fp32 accumulation throughout; the
 // result does not depend on workgroup scheduling.
 #include "api.h"
+#include "attn_decode_split.h"
 
 namespace bllm {
 
 BLLM_DEBUG_WORD(attn_decode_split)
-
-constexpr int SPL_THREADS = 256;
-constexpr int SPL_CHUNK = 256;  // keys per workgroup of the partial pass
 
 // the length this launch attends over: host L, or position + 1 (kept inside the cache)
 template <bool APPEND>
@@ -44,20 +42,6 @@ __device__ __forceinline__ int spl_len(int L, const int* __restrict__ pos, int p
   } else {
     return L < Tmax ? L : Tmax;
   }
-}
-
-// two 16-bit elements (one dword of a row) times two of q, added to c in fp32
-template <typename T>
-__device__ __forceinline__ float spl_dot2(uint32_t a, uint32_t b, float c);
-template <>
-__device__ __forceinline__ float spl_dot2<bf16_t>(uint32_t a, uint32_t b, float c) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 v2;
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2, a), __builtin_bit_cast(v2, b), c, false);
-}
-template <>
-__device__ __forceinline__ float spl_dot2<f16_t>(uint32_t a, uint32_t b, float c) {
-  typedef __attribute__((ext_vector_type(2))) _Float16 v2;
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(v2, a), __builtin_bit_cast(v2, b), c, false);
 }
 
 // RT query heads of one kv group per workgroup (H/G = RT * SUB, blockIdx.y = g * SUB + sub).
@@ -329,6 +313,35 @@ void attn_decode_split(DType dt, const void* q, const void* kc, const void* vc, 
 void attn_decode_append_split(DType dt, const void* qkv, void* kc, void* vc, void* out, float* ws, const int* pos,
                               int pos_stride, int B, int H, int G, int hd, int Tmax, hipStream_t s) {
   spl_dispatch<true>(dt, qkv, kc, vc, out, ws, pos, pos_stride, B, H, G, hd, Tmax, 0, s);
+}
+
+// The merge alone, per-row positions: for a partial pass that lives in another file and writes the
+// same workspace layout (attn_decode_fp8.hip).  Two template levels, as spl_dispatch / spl_launch:
+// the kernels are then instantiated after those of the two entry points above, which keeps the
+// order of the kernels in the code object (tools/isa_diff.py compares it as a text).
+template <typename T, int HD>
+static void spl_combine_launch(const float* ws, T* out, const int* pos, int B, int H, int Tmax, hipStream_t s) {
+  const int NCH = attn_decode_split_chunks(Tmax);
+  hipLaunchKernelGGL((attn_decode_split_combine_k<T, HD, true>), dim3(B * H), dim3(SPL_THREADS), 0, s, ws,
+                     ws + (long)B * H * NCH * HD, out, H, Tmax, NCH, 0, pos, 1);
+}
+
+template <bool ROWS>
+static void spl_combine_dispatch(DType dt, const float* ws, void* out, const int* pos, int B, int H, int hd, int Tmax,
+                                 hipStream_t s) {
+  static_assert(ROWS, "a position per row");
+  if (dt == DType::BF16) {
+    if (hd == 128) spl_combine_launch<bf16_t, 128>(ws, (bf16_t*)out, pos, B, H, Tmax, s);
+    else spl_combine_launch<bf16_t, 64>(ws, (bf16_t*)out, pos, B, H, Tmax, s);
+  } else {
+    if (hd == 128) spl_combine_launch<f16_t, 128>(ws, (f16_t*)out, pos, B, H, Tmax, s);
+    else spl_combine_launch<f16_t, 64>(ws, (f16_t*)out, pos, B, H, Tmax, s);
+  }
+}
+
+void attn_decode_split_combine_rows(DType dt, const float* ws, void* out, const int* pos, int B, int H, int hd,
+                                    int Tmax, hipStream_t s) {
+  spl_combine_dispatch<true>(dt, ws, out, pos, B, H, hd, Tmax, s);
 }
 
 }  // namespace bllm

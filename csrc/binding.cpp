@@ -770,6 +770,60 @@ Tensor attn_decode_split(const Tensor& q, const Tensor& kc, const Tensor& vc, in
 }
 int64_t attn_decode_split_chunk() { return bllm::attn_decode_split_chunk(); }
 
+// FP8 KV cache (csrc/attn_decode_fp8.hip): k8 / v8 [B, G, Tmax, hd] e4m3fn, ks / vs [B, G, Tmax] fp32,
+// all contiguous and 16-byte aligned; qkv bf16 / fp16, hd 64 or 128 -> (B, G, Tmax, hd) of the cache
+std::tuple<int64_t, int64_t, int64_t, int64_t> fp8_caches(const Op& op, const Tensor& qkv, const Tensor& k8,
+                                                          const Tensor& ks, const Tensor& v8, const Tensor& vs) {
+  op.half_only(qkv, "qkv");
+  op.contig(qkv, "qkv");
+  op.dims(qkv, 2, "qkv");
+  op.dims(k8, 4, "kcache");
+  const int64_t B = k8.size(0), G = k8.size(1), Tmax = k8.size(2), hd = k8.size(3);
+  op.shaped(k8, {B, G, Tmax, hd}, at::kFloat8_e4m3fn, "kcache");
+  op.like(v8, k8, "vcache");
+  op.shaped(ks, {B, G, Tmax}, at::kFloat, "kscale");
+  op.like(vs, ks, "vscale");
+  TORCH_CHECK(hd == 64 || hd == 128, op.name, ": head_dim 64 or 128, got ", hd);
+  TORCH_CHECK(B > 0 && G > 0 && Tmax > 0, op.name, ": empty cache ", k8.sizes());
+  op.to_int(Tmax, "Tmax");
+  TORCH_CHECK(aligned(qkv, 16) && aligned(k8, 16) && aligned(v8, 16) && aligned(ks, 4) && aligned(vs, 4), op.name,
+              ": qkv and the caches must be 16-byte aligned");
+  return {B, G, Tmax, hd};
+}
+
+// kv_cache_fill_varlen into an fp8 cache: rows t < len_b of (b, g) <- the quantised k / v of qkv
+// row cu[b] + t and their scales, nothing else written
+void kv_cache_fill_varlen_fp8(const Tensor& qkv, const Tensor& cu, Tensor& k8, Tensor& ks, Tensor& v8, Tensor& vs) {
+  Op op("kv_cache_fill_varlen_fp8", qkv, "qkv");
+  const auto [B, G, Tmax, hd] = fp8_caches(op, qkv, k8, ks, v8, vs);
+  TORCH_CHECK(qkv.size(1) % hd == 0 && qkv.size(1) / hd > 2 * G, "kv_cache_fill_varlen_fp8: qkv ", qkv.sizes(),
+              " is not [N, (H + 2G) hd] for the cache's G ", G, " and hd ", hd);
+  op.vec(cu, B + 1, at::kInt, "cu");
+  bllm::kv_cache_fill_varlen_fp8(dt_of(qkv), qkv.data_ptr(), cu.data_ptr<int>(), k8.data_ptr(), ks.data_ptr<float>(),
+                                 v8.data_ptr(), vs.data_ptr<float>(), qkv.size(0), op.to_int(B, "B"),
+                                 op.to_int(qkv.size(1) / hd - 2 * G, "H"), op.to_int(G, "G"), (int)hd, (int)Tmax,
+                                 stream());
+}
+
+// attn_decode_append_rows on an fp8 cache: row b's new k / v are quantised into cache row pos[b]
+// (pos int32 [B], the caller keeps every position < Tmax) and its query attends over the
+// dequantised keys 0..pos[b] -> out [B, H*hd]
+Tensor attn_decode_append_rows_fp8(const Tensor& qkv, Tensor& k8, Tensor& ks, Tensor& v8, Tensor& vs,
+                                   const Tensor& pos, int64_t H, int64_t G) {
+  Op op("attn_decode_append_rows_fp8", qkv, "qkv");
+  const auto [B, Gc, Tmax, hd] = fp8_caches(op, qkv, k8, ks, v8, vs);
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0 && Gc == G && qkv.size(0) == B && qkv.size(1) == (H + 2 * G) * hd,
+              "attn_decode_append_rows_fp8: qkv ", qkv.sizes(), " / cache ", k8.sizes(), " mismatch for H ", H, " G ",
+              G);
+  op.vec(pos, B, at::kInt, "pos");
+  auto ws = decode_split_scratch(op, qkv, B, H, G, hd, Tmax);
+  auto out = at::empty({B, H * hd}, qkv.options());
+  bllm::attn_decode_append_rows_fp8(dt_of(qkv), qkv.data_ptr(), k8.data_ptr(), ks.data_ptr<float>(), v8.data_ptr(),
+                                    vs.data_ptr<float>(), out.data_ptr(), ws.data_ptr<float>(), pos.data_ptr<int>(),
+                                    (int)B, (int)H, (int)G, (int)hd, (int)Tmax, stream());
+  return out;
+}
+
 // qkv [B T, (H + 2G) hd] contiguous; B, T, H, G, hd positive, H a multiple of G -> them as ints
 struct AttnDims { int B, T, H, G, hd; };
 AttnDims attn_args(const Op& op, const Tensor& qkv, int64_t B, int64_t T, int64_t H, int64_t G, int64_t hd) {
@@ -1377,8 +1431,8 @@ Tensor sample_rows(const Tensor& logits, const Tensor& streams, Tensor& ctr, int
 // instrumented translation unit; always 0 in release builds (the checks are compiled away).
 int64_t debug_error() {
   const unsigned codes[] = {bllm::debug_take_embedding(), bllm::debug_take_loss(), bllm::debug_take_attn_decode(),
-                            bllm::debug_take_attn_decode_split(), bllm::debug_take_elementwise(),
-                            bllm::debug_take_sample()};
+                            bllm::debug_take_attn_decode_split(), bllm::debug_take_attn_decode_fp8(),
+                            bllm::debug_take_elementwise(), bllm::debug_take_sample()};
   for (unsigned c : codes)
     if (c) return (int64_t)c;
   return 0;
@@ -1437,6 +1491,8 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("attn_decode_split(Tensor q, Tensor kcache, Tensor vcache, int L) -> Tensor", attn_decode_split);
   BLLM_OP("attn_decode_append_split(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_split);
   BLLM_OP("kv_cache_fill_varlen(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) vcache) -> ()", kv_cache_fill_varlen);
+  BLLM_OP("kv_cache_fill_varlen_fp8(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale) -> ()", kv_cache_fill_varlen_fp8);
+  BLLM_OP("attn_decode_append_rows_fp8(Tensor qkv, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale, Tensor pos, int H, int G) -> Tensor", attn_decode_append_rows_fp8);
   BLLM_OP("rope_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, int H, int G, int hd, Tensor pos) -> ()", rope_dev_);
   BLLM_OP("rope_pos_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos_ids, int H, int G, int hd, bool inverse) -> ()", rope_pos_);
   BLLM_OP("flash_attn_varlen_fwd(Tensor qkv, Tensor cu, int max_len, int H, int G, int hd) -> (Tensor, Tensor)", flash_attn_varlen_fwd);

@@ -27,7 +27,14 @@ and the split-KV kernels forced through ``ops.DECODE_SPLIT_MIN = 0``; past that 
 graph replay (the append op: split-KV at every position of such a cache) and the eager loop (the
 plain op, which goes by the number of keys: single-launch up to 8,192 keys, split-KV beyond).  One JSON line: median and range
 of ms per generated token per arm (prefill included in the wall time, and reported on its own).
-Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 32768 --prompt 200"""
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 32768 --prompt 200
+
+``--context N --kv_dtype fp8``: the cache format instead.  ``generate_ragged``, greedy, graph replay,
+``--batch`` rows of ``--prompt`` random tokens: the cache in the parameter dtype against the fp8
+cache, interleaved as above; ``--kv_arms fp8`` runs the fp8 arm alone (a batch whose bf16 cache
+does not fit).  One JSON line: ms per generated token per arm (``kv_model``, ``kv_fp8``), and each arm's
+cache bytes.
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 32768 --prompt 8192 --kv_dtype fp8"""
 import argparse
 import json
 import os
@@ -180,6 +187,50 @@ def context_bench(a, m, cfg):
             json.dump([row], f, indent=1)
 
 
+def kv_bench(a, m, cfg):
+    ctx = cfg.context_length
+    if a.prompt + a.tokens > ctx:
+        sys.exit(f"bench_decode: prompt ({a.prompt}) + tokens ({a.tokens}) exceed --context ({ctx})")
+    g = torch.Generator().manual_seed(1)
+    prompts = [torch.randint(0, cfg.vocab_size, (a.prompt,), generator=g) for _ in range(a.batch)]
+    arms = {k: (None if k == "model" else k) for k in a.kv_arms.split(",")}
+
+    def run(arm, tokens):
+        return G.generate_ragged(m, prompts, tokens, ctx, kv_dtype=arms[arm])
+
+    def cache_bytes(arm):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        cache = m.new_kv_cache(a.batch, ctx, kv_dtype=arms[arm])
+        used = torch.cuda.max_memory_allocated() - base
+        del cache
+        return used
+
+    nbytes = {k: cache_bytes(k) for k in arms}
+    for k in arms:                                     # warm-up of each arm
+        run(k, a.tokens)
+    times = {k: [] for k in arms}
+    prefill = {k: [] for k in arms}
+    for _ in range(a.repeats):
+        for k in arms:
+            times[k].append(_timed(lambda: run(k, a.tokens)))
+            prefill[k].append(_timed(lambda: run(k, 1)))
+    row = {"model": f"{a.model}-{a.num_params}", "context": ctx, "batch": a.batch, "prompt_tokens": a.prompt,
+           "new_tokens": a.tokens, "repeats": a.repeats, "graph": os.environ.get("BLLM_DECODE_GRAPH", "default")}
+    for k in arms:
+        ms = sorted(1000 * t / a.tokens for t in times[k])
+        row["kv_" + k] = {"ms_per_token": round(statistics.median(ms), 4), "ms_per_token_range": [round(ms[0], 4), round(ms[-1], 4)],
+                  "prefill_ms": round(1000 * statistics.median(prefill[k]), 3), "cache_bytes": nbytes[k]}
+    if len(arms) == 2:
+        row["fp8_no_slower"] = row["kv_fp8"]["ms_per_token"] <= row["kv_model"]["ms_per_token_range"][1]
+    print(json.dumps(row), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump([row], f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3")
@@ -197,6 +248,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--context", type=int, default=None,
                     help="model context = KV-cache length; compares the decode-attention kernels (see above)")
+    ap.add_argument("--kv_dtype", default="model", choices=["model", "fp8"],
+                    help="--context: fp8 compares the KV-cache formats through generate_ragged (see above)")
+    ap.add_argument("--kv_arms", default="model,fp8", help="--kv_dtype fp8: the arms to run")
     a = ap.parse_args()
     ops.load_ext(required=True)
     cfg = (get_config(a.model, a.num_params) if a.context is None
@@ -209,7 +263,7 @@ def main():
     if a.ragged:
         return ragged_sampling(a, m, cfg) if a.temperature > 0 else ragged(a, m, cfg)
     if a.context is not None:
-        return context_bench(a, m, cfg)
+        return kv_bench(a, m, cfg) if a.kv_dtype == "fp8" else context_bench(a, m, cfg)
     idx = torch.randint(0, cfg.vocab_size, (a.batch, a.prompt), device="cuda")
     g = torch.Generator(device="cuda").manual_seed(1)
     G.generate_cached(m, idx, 8, cfg.context_length, temperature=1.0, top_k=5, generator=g)  # warm-up
