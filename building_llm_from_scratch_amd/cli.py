@@ -49,6 +49,8 @@ def perform_checks(args):
         raise ValueError("--generate_seed must fit 64 bits.")
     if getattr(args, "generate_kv_dtype", "model") not in ("model", "fp8"):
         raise ValueError("--generate_kv_dtype must be 'model' or 'fp8'.")
+    if getattr(args, "generate_weight_dtype", "model") not in ("model", "fp8"):
+        raise ValueError("--generate_weight_dtype must be 'model' or 'fp8'.")
     if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -181,6 +183,11 @@ def build_parser() -> argparse.ArgumentParser:
     x.add_argument("--generate_kv_dtype", type=str, default="model",
                    help="KV cache of --generate_prompts: 'model' keeps it in the parameter dtype; 'fp8' stores e4m3 bytes "
                         "with one fp32 scale per (row, kv head, position), about half the bytes (answers can differ)")
+    x.add_argument("--generate_weight_dtype", type=str, default="model",
+                   help="weights of the decode steps of --generate_prompts: 'model' uses the model's own; 'fp8' runs "
+                        "every projection on e4m3 packs with one fp32 scale per output channel, LoRA folded in, built "
+                        "once per run of the prompts (extra memory, about half the 16-bit weights; the first token "
+                        "of an answer still comes from the exact weights; answers can differ)")
     x.add_argument("--generate_only", action="store_true",
                    help="no data preparation, training or final save: build the model (--load_weights / "
                         "--resume), answer --generate_prompts, exit")
@@ -268,6 +275,8 @@ def _generate_responses(trainer, args, rank, out_dir):
                         seed=args.generate_seed)
     if getattr(args, "generate_kv_dtype", "model") == "fp8":
         sampling["kv_dtype"] = "fp8"
+    if getattr(args, "generate_weight_dtype", "model") == "fp8":
+        sampling["weight_dtype"] = "fp8"
     responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size, **sampling)
     if rank != 0:
         return

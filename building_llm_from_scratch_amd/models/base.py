@@ -365,6 +365,11 @@ class _HeadLogitsFn(torch.autograd.Function):
         return dx, None
 
 
+# Decode-only fp8 weights (BaseLM.new_decode_weights): blocks[i] = the LinearW8 of block i's
+# projection groups in ``w8_groups()`` order, head = the head's
+DecodeWeights = namedtuple("DecodeWeights", "blocks head")
+
+
 # ---------------------------------------------------------------------------
 class BaseLM(nn.Module):
     """Common machinery for GPTModel / Llama models."""
@@ -660,13 +665,44 @@ class BaseLM(nn.Module):
         return comps[-1].infer_rows(x, (seq.cu[1:] - 1).to(torch.long))
 
     @torch.no_grad()
-    def forward_cached_rows(self, idx: torch.Tensor, cache, pos_rows: torch.Tensor) -> torch.Tensor:
+    def new_decode_weights(self, weight_dtype: str = "fp8") -> "DecodeWeights":
+        """Decode-only fp8 packs of every projection: per block one :class:`LinearW8` per group
+        (Llama: qkv, o, gate/up, down; GPT-2: qkv, o, fc, proj, with their biases) and one for the
+        head (vocabulary rows), each the ``ops.w8_pack`` of the group's effective weight -- e4m3fn
+        bytes, one fp32 scale per output channel, LoRA folded in (``FusedLinear.w8_pack``).  Norm
+        weights and embeddings are not packed.  For :meth:`forward_cached_rows` only: the prefill
+        (:meth:`forward_prefill_ragged`) always runs on the model's own weights, so the first new
+        token comes from exact logits and every later step from the quantised weights.
+
+        A snapshot of the weights as they are now, and extra memory on top of them (about half
+        the bytes of 16-bit weights): a speed feature, not a capacity one.  Call inside
+        ``engine.params_resident()`` (a sharding FSDP engine then hands it whole weights)."""
+        if weight_dtype != "fp8":
+            raise ValueError(f"new_decode_weights: weight_dtype must be 'fp8', got {weight_dtype!r}")
+        self._ensure_flat()
+        self._rctx.sync_all_params()
+        comps = self._comps
+        return DecodeWeights([tuple(fl.w8_pack() for fl in c.w8_groups()) for c in comps[1:-1]],
+                             comps[-1].head.w8_pack())
+
+    @torch.no_grad()
+    def forward_cached_rows(self, idx: torch.Tensor, cache, pos_rows: torch.Tensor, weights=None) -> torch.Tensor:
         """:meth:`forward_cached_dev` with a position per row: one decode token per row (idx [B, 1]),
         row b at ``pos_rows[b]`` (int32 [B] on the device, each below the cache length and the
         model's context length -- the caller's entry check, train/generate.py:generate_ragged).
-        No host read, so the step can be captured in a HIP graph wherever :meth:`decode_graph_ok`."""
+        No host read, so the step can be captured in a HIP graph wherever :meth:`decode_graph_ok`.
+
+        ``weights`` (:meth:`new_decode_weights`): every projection of the step, the head's
+        included, runs on its fp8 pack (``ops.linear_w8``) instead of the model's weights; norms,
+        embeddings, RoPE and attention are unchanged.  ``None``: exactly the step above."""
         comps = self._comps
         x = comps[0].infer_rows(idx, pos_rows)
+        if weights is not None:
+            if not isinstance(weights, DecodeWeights) or len(weights.blocks) != len(comps) - 2:
+                raise ValueError("forward_cached_rows: weights must be this model's new_decode_weights()")
+            for c, kv, w in zip(comps[1:-1], cache, weights.blocks):
+                x = c.infer_rows(x, pos_rows, kv, weights=w)
+            return comps[-1].infer(x, idx.shape[0], 1, weights=weights.head)
         for c, kv in zip(comps[1:-1], cache):
             x = c.infer_rows(x, pos_rows, kv)
         return comps[-1].infer(x, idx.shape[0], 1)

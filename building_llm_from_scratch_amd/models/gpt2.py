@@ -173,20 +173,34 @@ class GPTBlockCompute(UnitCompute):
         m, _ = self.proj.forward(ops.gelu_fwd(f))
         return x2 + m
 
-    def _infer_out(self, x2d, o):
+    def w8_groups(self):
+        """The block's projection groups, in the order of its entry in ``new_decode_weights``."""
+        return (self.qkv, self.o, self.fc, self.proj)
+
+    def _infer_out(self, x2d, o, weights=None):
         """Everything after attention (inference: no dropout): out projection, residual, GELU MLP."""
         b = self.block
+        if weights is not None:
+            x2 = x2d + self.o.forward_w8(o, weights[1])
+            f = self.fc.forward_w8(self._ln(x2, b.norm2)[0], weights[2])
+            return x2 + self.proj.forward_w8(ops.gelu_fwd(f), weights[3])
         a, _ = self.o.forward(o)
         x2 = x2d + a
         f, _ = self.fc.forward(self._ln(x2, b.norm2)[0])
         m, _ = self.proj.forward(ops.gelu_fwd(f))
         return x2 + m
 
-    def infer_rows(self, x2d, pos_rows, kv):
-        """``infer_dev`` with a position per row (int32 [B] on the device)."""
+    def infer_rows(self, x2d, pos_rows, kv, weights=None):
+        """``infer_dev`` with a position per row (int32 [B] on the device).  ``weights``: the
+        block's fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``."""
         H = self.rctx.cfg.n_heads
-        qkv, _ = self.qkv.forward(self._ln(x2d, self.block.norm1)[0])
-        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, H, scales=kv[2:]))
+        h1 = self._ln(x2d, self.block.norm1)[0]
+        if weights is not None:
+            qkv = self.qkv.forward_w8(h1, weights[0])
+        else:
+            qkv, _ = self.qkv.forward(h1)
+        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, H, scales=kv[2:]),
+                               weights)
 
     def infer_ragged(self, x2d, seq, kv):
         """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,

@@ -52,8 +52,12 @@ class HeadComputeMixin:
         super().bind(unit)
         self.head.bind(unit)
 
-    def infer(self, x2d, B, t):
+    def infer(self, x2d, B, t, weights=None):
+        """Logits of each row's last position.  ``weights``: the head's fp8 pack
+        (``new_decode_weights``: vocabulary rows, one scale each); the projection is ``forward_w8``."""
         last = x2d.view(B, t, -1)[:, -1, :].contiguous()
+        if weights is not None:
+            return self.head.forward_w8(self._norm_fwd(last)[0], weights)
         logits, _ = self.forward_logits(last, save=False)
         return logits
 

@@ -225,6 +225,11 @@ GroupedCtx = namedtuple("GroupedCtx", "t P")
 LowRankDx = namedtuple("LowRankDx", "base u P scale")
 
 
+# a projection group for the decode step on fp8 weights: the ops.W8Pack of its effective weight
+# (LoRA folded in) and its bias or None (FusedLinear.w8_pack / forward_w8)
+LinearW8 = namedtuple("LinearW8", "pack bias")
+
+
 class FrozenDerived:
     """Something built from a frozen weight, rebuilt only when the weight's storage or version
     changed (a re-gather, a state-dict load)."""
@@ -407,6 +412,28 @@ class FusedLinear:
                 y[:, c0:c1].addmm_(t, B, alpha=s.scaling)
                 xa.append(t)
         return y, xa
+
+    # ------------------------------------------------------------------ fp8 decode weights
+    def w8_pack(self) -> "LinearW8":
+        """The group's decode-only fp8 pack (``ops.w8_pack``: e4m3fn bytes, one fp32 scale per
+        output channel) of its effective weight -- the fused W plus ``scaling * (A B)^T`` in every
+        LoRA member's rows, formed in fp32 and then quantised, so a decode step on the pack runs no
+        rank-r kernel -- and a copy of its bias.  A snapshot: it does not follow later updates of
+        the weights."""
+        W = self.W().detach().to(torch.float32, copy=self.has_lora)
+        for (c0, c1), s in zip(self.cols, self.specs):
+            if s.lora_A is not None:
+                A, B = self.unit.data(s.lora_A).float(), self.unit.data(s.lora_B).float()
+                W[c0:c1] += s.scaling * (A @ B).t()
+        b = self.b()
+        return LinearW8(ops.w8_pack(W), None if b is None else b.detach().clone())
+
+    def forward_w8(self, x: torch.Tensor, pack: "LinearW8", residual: Optional[torch.Tensor] = None):
+        """``forward`` on the group's fp8 pack: one ``ops.linear_w8`` call (bias or residual in its
+        epilogue, LoRA already folded into the pack) -> y."""
+        if residual is not None:
+            assert pack.bias is None
+        return ops.linear_w8(x, pack.pack, pack.bias, residual)
 
     def forward_swiglu(self, x: torch.Tensor):
         """Gate/up projection with the SwiGLU forward in the GEMM epilogue (``[fc1; fc2]``, no

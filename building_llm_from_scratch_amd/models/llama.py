@@ -267,29 +267,42 @@ class LlamaBlockCompute(UnitCompute):
         x3, _ = self.down.forward(ops.swiglu_fwd(gu), residual=x2)
         return x3
 
-    def _infer_qkv(self, x2d):
+    def w8_groups(self):
+        """The block's projection groups, in the order of its entry in ``new_decode_weights``."""
+        return (self.qkv, self.o, self.gu, self.down)
+
+    def _infer_qkv(self, x2d, weights=None):
         u, b = self.unit, self.block
         h1, _ = ops.rmsnorm_fwd(x2d, u.data(b.norm1.weight), self.rctx.cfg.norm_eps)
+        if weights is not None:
+            return self.qkv.forward_w8(h1, weights[0])
         return self.qkv.forward(h1)[0]
 
-    def _infer_out(self, x2d, o):
+    def _infer_out(self, x2d, o, weights=None):
         """Everything after attention: out projection + residual, norm2, SwiGLU MLP + residual."""
         u, b = self.unit, self.block
+        if weights is not None:
+            x2 = self.o.forward_w8(o, weights[1], residual=x2d)
+            h2, _ = ops.rmsnorm_fwd(x2, u.data(b.norm2.weight), self.rctx.cfg.norm_eps)
+            gu = self.gu.forward_w8(h2, weights[2])
+            return self.down.forward_w8(ops.swiglu_fwd(gu), weights[3], residual=x2)
         x2, _ = self.o.forward(o, residual=x2d)
         h2, _ = ops.rmsnorm_fwd(x2, u.data(b.norm2.weight), self.rctx.cfg.norm_eps)
         gu, _ = self.gu.forward(h2)
         x3, _ = self.down.forward(ops.swiglu_fwd(gu), residual=x2)
         return x3
 
-    def infer_rows(self, x2d, pos_rows, kv):
+    def infer_rows(self, x2d, pos_rows, kv, weights=None):
         """``infer_dev`` with a position per row (int32 [B] on the device): RoPE rotates row b at
-        ``pos_rows[b]`` and the decode kernel appends and attends there."""
+        ``pos_rows[b]`` and the decode kernel appends and attends there.  ``weights``: the block's
+        fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``."""
         cfg = self.rctx.cfg
         H, G, hd = cfg.n_heads, cfg.n_kv_groups, cfg.head_dim
         cos, sin = self.rctx.rope
-        qkv = self._infer_qkv(x2d)
+        qkv = self._infer_qkv(x2d, weights)
         ops.rope_pos_(qkv, cos, sin, pos_rows, H, G, hd)
-        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G, scales=kv[2:]))
+        return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G, scales=kv[2:]),
+                               weights)
 
     def infer_ragged(self, x2d, seq, kv):
         """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,

@@ -12,7 +12,7 @@ range, common.h ``BLLM_DASSERT``) raises at the op that caused it, like a launch
 from __future__ import annotations
 
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -31,6 +31,7 @@ __all__ = [
     "lora_down_into", "lora_block_", "rmsnorm_fwd_into", "swiglu_fwd_into", "sum_partials_",
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
     "gemm_nn_", "gemm_nt_", "gemm_nn_ok", "dgrad_gemm_enabled", "transpose2d", "dgrad_wt_enabled", "attn_keep_mask",
+    "W8Pack", "w8_pack", "w8_unpack", "linear_w8",
 ]
 
 rope_tables = ref.rope_tables
@@ -526,6 +527,73 @@ def linear_residual(x: torch.Tensor, W: torch.Tensor, C: torch.Tensor) -> torch.
             and C.dtype == x.dtype and x.is_contiguous() and W.is_contiguous() and C.is_contiguous()):
         return _k().linear_residual(x, W, C)
     return torch.addmm(C, x, W.t())
+
+
+# --------------------------------------------------------------------------- fp8 decode weights
+W8_ROW_TILE = 16     # rows of a pack tile (csrc/linear_w8.hip W8_TN: one v_mfma_f32_16x16x32 A operand)
+W8_K_GRANULE = 64    # k per 1-KiB block of a tile (W8_KG): 64 lanes x 16 bytes
+W8_WAVES = 8         # waves of a workgroup = contiguous K slices (W8_WAVES)
+
+
+class W8Pack(NamedTuple):
+    """A weight ``W [N, K]`` in the fp8 format of ``kv_quantize_rows`` over its rows (e4m3fn bytes
+    ``q [N, K]``, fp32 ``scale [N]``; dequantised weight ``q.float() * scale[:, None]``).
+
+    ``data`` (uint8, 1-D) holds the bytes.  ``tiled``: in the order csrc/linear_w8.hip streams
+    them -- N padded with zero rows to ``W8_ROW_TILE``, and for tile t and K block kb the KiB
+    ``[t][kb][g][r][b] = q[16 t + r][64 kb + 16 g + b]`` (g < 4, r < 16, b < 16), so that a wave's
+    16-byte load is contiguous and a lane's 16 bytes are its MFMA fragments of two k-steps.  Not
+    tiled (K is no multiple of ``W8_K_GRANULE``): row-major, for the oracle path only.  Padding
+    rows have no scale: they are never stored."""
+    data: torch.Tensor
+    scale: torch.Tensor
+    N: int
+    K: int
+    tiled: bool
+
+
+def w8_pack(W: torch.Tensor) -> W8Pack:
+    """Quantise and lay out a weight [N, K] (any float dtype, any device) for ``linear_w8``.  Torch
+    ops only (it runs once per generation call, not per step); the same values give the same bytes
+    and scale bits on the CPU and on the GPU."""
+    if W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+        raise ValueError(f"w8_pack: W must be [N, K], got {tuple(W.shape)}")
+    N, K = W.shape
+    q, s = ref.kv_quantize_rows(W)
+    q = q.view(torch.uint8)
+    if K % W8_K_GRANULE:
+        return W8Pack(q.reshape(-1).contiguous(), s, N, K, False)
+    T = -(-N // W8_ROW_TILE)
+    if T * W8_ROW_TILE != N:
+        q = torch.cat([q, q.new_zeros(T * W8_ROW_TILE - N, K)], 0)
+    data = q.view(T, W8_ROW_TILE, K // W8_K_GRANULE, 4, 16).permute(0, 2, 3, 1, 4).reshape(-1).contiguous()
+    return W8Pack(data, s, N, K, True)
+
+
+def w8_unpack(pack: W8Pack):
+    """-> (q [N, K] float8_e4m3fn, scale [N] fp32): the inverse of ``w8_pack``, bit for bit."""
+    N, K = pack.N, pack.K
+    if not pack.tiled:
+        return pack.data.view(N, K).view(torch.float8_e4m3fn), pack.scale
+    T = -(-N // W8_ROW_TILE)
+    q = pack.data.view(T, K // W8_K_GRANULE, 4, W8_ROW_TILE, 16).permute(0, 3, 1, 2, 4).reshape(T * W8_ROW_TILE, K)
+    return q[:N].contiguous().view(torch.float8_e4m3fn), pack.scale
+
+
+def linear_w8(x: torch.Tensor, pack: W8Pack, bias: Optional[torch.Tensor] = None,
+              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y[m, n] = round(scale[n] * sum_k x[m, k] q[n, k] + bias[n] + residual[m, n])`` for x [M, K]
+    and an fp8 weight pack, fp32 accumulation, y in x's dtype (``ops.reference.linear_w8`` is the
+    contract).  bf16 / fp16 GPU tensors with a tiled pack run the HIP kernel (csrc/linear_w8.hip:
+    one launch, deterministic, a row of y independent of the other rows and of M, graph-capturable);
+    CPU tensors, fp32 and packs of other K run the oracle."""
+    if x.dim() != 2 or x.shape[1] != pack.K:
+        raise ValueError(f"linear_w8: x must be [M, {pack.K}], got {tuple(x.shape)}")
+    if x.device.type == "cuda" and x.dtype in (torch.bfloat16, torch.float16) and pack.tiled and x.shape[0] > 0:
+        load_ext(required=True)
+        return _k().linear_w8(x, pack.data, pack.scale, bias, residual)
+    q, s = w8_unpack(pack)
+    return ref.linear_w8(x, q, s, bias, residual)
 
 
 def transpose2d(a: torch.Tensor) -> torch.Tensor:

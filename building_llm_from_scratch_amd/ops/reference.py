@@ -620,6 +620,19 @@ def kv_cache_fill_varlen_fp8(qkv, cu, k8, v8, kscale, vscale):
             cs[b, :, :r1 - r0] = s
 
 
+# ------------------------------------------------------------------ fp8 decode weights (csrc/linear_w8.hip oracle)
+def linear_w8(x, q, s, bias=None, residual=None):
+    """Reference for the fp8-weight projection, in fp64: x [M, K], q [N, K] float8_e4m3fn and
+    s [N] fp32 (``kv_quantize_rows`` of a weight's rows) ->
+    ``y[m, n] = s[n] * sum_k x[m, k] q[n, k] + bias[n] + residual[m, n]`` in x's dtype."""
+    v = (x.double() @ q.double().t()) * s.double()
+    if bias is not None:
+        v = v + bias.double()
+    if residual is not None:
+        v = v + residual.double()
+    return v.to(x.dtype)
+
+
 # ------------------------------------------------------------------ LoRA (csrc/lora.hip oracle)
 def lora_down(x, ws, c0, lens, ocol, R: int, scale: float = 1.0):
     """out[:, ocol_i : ocol_i + r_i] = scale * x[:, c0_i : c0_i + len_i] @ w_i[:, :len_i]^T"""

@@ -194,8 +194,9 @@ class RowsDecodeGraph:
     ``next_idx=idx``); the position increment is captured too, so a token is one :meth:`replay`
     and nothing else.  It is not called during the warm-up passes, whose logits mean nothing."""
 
-    def __init__(self, model, cache, pos: torch.Tensor, device, sampler=None):
+    def __init__(self, model, cache, pos: torch.Tensor, device, sampler=None, weights=None):
         B, Tmax = pos.numel(), cache[0][0].shape[2]
+        kw = {} if weights is None else {"weights": weights}   # fp8 decode weights: warm-up and capture on them
         self.idx = torch.zeros(B, 1, dtype=torch.long, device=device)
         self.pos = torch.full((B,), Tmax - 1, dtype=torch.int32, device=device)
         cur = torch.cuda.current_stream(device)
@@ -203,11 +204,11 @@ class RowsDecodeGraph:
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             for _ in range(2):
-                model.forward_cached_rows(self.idx, cache, self.pos)
+                model.forward_cached_rows(self.idx, cache, self.pos, **kw)
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.logits = model.forward_cached_rows(self.idx, cache, self.pos)
+            self.logits = model.forward_cached_rows(self.idx, cache, self.pos, **kw)
             if sampler is not None:
                 sampler(self.logits, self.idx)
                 self.pos.add_(1)
@@ -228,7 +229,8 @@ class RowsDecodeGraph:
 def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temperature: float = 0.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
-                    seed: Optional[int] = None, streams=None, kv_dtype: Optional[str] = None) -> list:
+                    seed: Optional[int] = None, streams=None, kv_dtype: Optional[str] = None,
+                    weight_dtype=None) -> list:
     """Batched KV-cache generation from prompts of different lengths.
 
     ``prompts``: a non-empty list of non-empty 1-D LongTensors.  Returns one 1-D tensor per prompt:
@@ -263,11 +265,22 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     position) (``model.new_kv_cache``): about half the cache bytes.  The prefill attention still
     runs on the exact K / V of the packed rows; what is stored, and what every later step attends
     over, is quantised, so the tokens can differ from the default cache's.  None: the cache in the
-    parameter dtype, as before."""
+    parameter dtype, as before.
+
+    ``weight_dtype="fp8"`` runs every decode step's projections, the head's included, on fp8
+    packs of the weights (``model.new_decode_weights``: e4m3fn bytes, one scale per output
+    channel, LoRA folded in; ``ops.linear_w8``), built once inside the call; a pack the caller
+    built already (``model.new_decode_weights()``) is taken as it is.  The prefill runs on the
+    model's own weights, so the first new token comes from exact logits; every later one from the
+    quantised weights, so the tokens can differ from the default's.  The packs are extra memory,
+    about half the bytes of 16-bit weights.  None: the model's weights, as before."""
     from .. import ops
-    from ..models.base import pack_prompts
+    from ..models.base import DecodeWeights, pack_prompts
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate_ragged: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+    if weight_dtype is not None and weight_dtype != "fp8" and not isinstance(weight_dtype, DecodeWeights):
+        raise ValueError("generate_ragged: weight_dtype must be None, 'fp8' or the model's new_decode_weights(), "
+                         f"got {weight_dtype!r}")
     if not isinstance(prompts, (list, tuple)) or len(prompts) == 0:
         raise ValueError("generate_ragged: prompts must be a non-empty list of 1-D token tensors")
     for b, p in enumerate(prompts):
@@ -300,6 +313,9 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
             model.new_kv_cache(B, context_size, kv_dtype=kv_dtype)
         logits = model.forward_prefill_ragged(idx, seq, cache)
         dec = None
+        kw = {}
+        if weight_dtype is not None:
+            kw["weights"] = model.new_decode_weights("fp8") if weight_dtype == "fp8" else weight_dtype
         if sampler is not None:
             stream_t = torch.tensor(sampler[2], dtype=torch.long).to(device)
             ctr = torch.zeros(B, dtype=torch.int32, device=device)    # row b has drawn ctr[b] tokens
@@ -313,7 +329,7 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
             draw(logits, nxt)
             n = 1
             if new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
-                dec = RowsDecodeGraph(model, cache, pos, device, sampler=draw)
+                dec = RowsDecodeGraph(model, cache, pos, device, sampler=draw, **kw)
                 dec.idx.copy_(nxt)
             while n < new:
                 if eos_id is not None and n - checked >= EOS_CHECK_EVERY:
@@ -323,13 +339,13 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
                 if dec is not None:
                     dec.replay()
                 else:
-                    logits = model.forward_cached_rows(nxt, cache, pos)
+                    logits = model.forward_cached_rows(nxt, cache, pos, **kw)
                     pos += 1
                     draw(logits, nxt)
                 n += 1
         elif new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
             logits = logits.clone()            # the prefill output must survive the capture
-            dec = RowsDecodeGraph(model, cache, pos, device)
+            dec = RowsDecodeGraph(model, cache, pos, device, **kw)
         for i in range(new if sampler is None else 0):
             idx_next = _sample(logits, temperature, top_k, generator)
             out[:, i] = idx_next[:, 0]
@@ -345,7 +361,7 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
             if dec is not None:
                 logits = dec.step(idx_next)
             else:
-                logits = model.forward_cached_rows(idx_next, cache, pos)
+                logits = model.forward_cached_rows(idx_next, cache, pos, **kw)
                 pos += 1
     gen = out[:, :n]
     if eos_id is not None:

@@ -496,7 +496,7 @@ class Trainer:
         return decoded
 
     def generate_responses(self, prompts, max_new_tokens: int, batch_size: int, temperature: float = 0.0,
-                           top_k=None, top_p=None, seed=None, kv_dtype=None):
+                           top_k=None, top_p=None, seed=None, kv_dtype=None, weight_dtype=None):
         """Continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in input
         order, each cut before its first eos: greedy by default; with ``seed`` sampled on the
         device (``temperature``, ``top_k``, ``top_p``: :func:`generate_ragged`), prompt i drawing
@@ -506,7 +506,12 @@ class Trainer:
         one :func:`generate_ragged` call.  Every rank must call this with the same prompts (the
         engines gather parameters collectively, as for the sample print).  A prompt longer than
         ``context_length - max_new_tokens`` raises ValueError naming its index, before any
-        generation.  ``kv_dtype="fp8"``: the quantised KV cache of :func:`generate_ragged`."""
+        generation.  ``kv_dtype="fp8"``: the quantised KV cache of :func:`generate_ragged`.
+        ``weight_dtype="fp8"``: its fp8 decode weights; the packs are built once here, from the
+        weights as they are now, shared by every batch and dropped on return (nothing is kept
+        across calls: the weights may change in between)."""
+        if weight_dtype not in (None, "fp8"):
+            raise ValueError(f"generate_responses: weight_dtype must be None or 'fp8', got {weight_dtype!r}")
         tok, cfg = self.loaderObj.tokenizer, self.config
         ctx = cfg["context_length"]
         ids = [text_to_token_ids(t, tok, cfg)[0] for t in prompts]
@@ -518,12 +523,19 @@ class Trainer:
                                  f"not fit the context length {ctx}")
         order = sorted(range(len(ids)), key=lambda i: ids[i].numel())
         out = [None] * len(ids)
+        weights = None
+        if weight_dtype is not None:
+            eng = self.model.rctx.engine
+            with eng.params_resident() if hasattr(eng, "params_resident") else contextlib.nullcontext():
+                weights = self.model.new_decode_weights(weight_dtype)
         for s in range(0, len(order), max(1, int(batch_size))):
             rows = order[s:s + max(1, int(batch_size))]
             sampling = {} if seed is None else dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                                     streams=rows)
             if kv_dtype is not None:
                 sampling["kv_dtype"] = kv_dtype
+            if weights is not None:
+                sampling["weight_dtype"] = weights
             res = generate_ragged(self.model, [ids[i] for i in rows], max_new_tokens, ctx, eos_id=cfg["eos_id"],
                                   **sampling)
             for i, r in zip(rows, res):

@@ -295,6 +295,15 @@ void gemm_nt_rope(DType dt, const void* a, long lda, const void* w, long ldw, vo
 void gemm_nt_swiglu(DType dt, const void* a, long lda, const void* w, long ldw, void* gu, long ldgu, void* act, int M,
                     int F, int K, hipStream_t s);
 
+// linear_w8.hip — y[M, N] = x[M, K] . dequant(pack)^T (+ bias[N]) (+ res[M, N]) for bf16 / fp16 x:
+// pack = the e4m3fn bytes of W [N, K] in the tile order of ops.w8_pack (N padded to row tiles,
+// K whole granules), scale fp32 [N] (the format of kv_quantize_rows over the rows of W)
+int linear_w8_row_tile();    // ops.W8_ROW_TILE
+int linear_w8_k_granule();   // ops.W8_K_GRANULE
+bool linear_w8_supported(int M, int N, int K);
+void linear_w8(DType dt, const void* x, const void* wp, const float* scale, const void* bias, const void* res,
+               void* y, int M, int N, int K, hipStream_t s);
+
 // optim.hip
 void adamw_step(DType pdt, DType gdt, void* param, float* master, const void* grad, float* m, float* v, long n,
                 double lr, double b1, double b2, double eps, double wd, int step, const float* gscale,

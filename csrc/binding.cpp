@@ -1384,6 +1384,35 @@ Tensor linear_residual(const Tensor& x, const Tensor& W, const Tensor& C) {
   return D;
 }
 
+// ------------------------------------------------------------------ fp8-weight projection
+// y [M, N] = x [M, K] . dequant(pack)^T (+ bias [N]) (+ residual [M, N]) (csrc/linear_w8.hip):
+// x bf16 / fp16; packed = the bytes of ops.w8_pack (uint8, N padded to row tiles, times K);
+// scale fp32 [N], which also gives N; bias / residual of x's dtype
+Tensor linear_w8(const Tensor& x, const Tensor& packed, const Tensor& scale, const optional<Tensor>& bias_,
+                 const optional<Tensor>& residual_) {
+  Op op("linear_w8", x, "x");
+  op.half_only(x, "x");
+  op.contig(x, "x");
+  op.dims(x, 2, "x");
+  op.dims(scale, 1, "scale");
+  const int64_t M = x.size(0), K = x.size(1), N = scale.size(0), TN = bllm::linear_w8_row_tile();
+  op.vec(scale, N, at::kFloat, "scale");
+  const int m = op.to_int(M, "M"), n = op.to_int(N, "N"), k = op.to_int(K, "K");
+  TORCH_CHECK(bllm::linear_w8_supported(m, n, k), op.name, ": x ", x.sizes(), " with ", N,
+              " output rows: M, N >= 1 and K a positive multiple of ", bllm::linear_w8_k_granule());
+  op.vec(packed, (N + TN - 1) / TN * TN * K, at::kByte, "packed");
+  const Tensor* bias = opt(bias_);
+  const Tensor* res = opt(residual_);
+  if (bias) op.vec(*bias, N, x.scalar_type(), "bias");
+  if (res) op.shaped(*res, {M, N}, x.scalar_type(), "residual");
+  TORCH_CHECK(aligned(x, 16) && aligned(packed, 16) && aligned(scale, 4) && (!res || aligned(*res, 16)), op.name,
+              ": x, packed and residual must be 16-byte aligned");
+  auto y = at::empty({M, N}, x.options());
+  bllm::linear_w8(dt_of(x), x.data_ptr(), packed.data_ptr(), scale.data_ptr<float>(), opt_ptr(bias), opt_ptr(res),
+                  y.data_ptr(), m, n, k, stream());
+  return y;
+}
+
 // ------------------------------------------------------------------ sampler
 // logits [B, V] -> tokens int64 [B]: temperature (0: argmax), top-k (0 or >= V: off), top-p (1: off)
 // and a Gumbel-max draw from the counter-based stream (seed, stream[b], ctr[b]) (csrc/sample.hip).
@@ -1466,6 +1495,7 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("bwd_bias_grad_(Tensor(a!) src, Tensor? aux, Tensor(b!)? db, bool accumulate, int op, float p, int seed, int offset, bool act_inplace=False) -> Tensor", bwd_bias_grad_);
   BLLM_OP("transpose2d(Tensor a) -> Tensor", transpose2d);
   BLLM_OP("linear_residual(Tensor x, Tensor W, Tensor C) -> Tensor", linear_residual);
+  BLLM_OP("linear_w8(Tensor x, Tensor packed, Tensor scale, Tensor? bias, Tensor? residual) -> Tensor", linear_w8);
   BLLM_OP("swiglu_fwd(Tensor gu) -> Tensor", swiglu_fwd);
   BLLM_OP("swiglu_fwd_into_(Tensor gu, Tensor(a!) act) -> ()", swiglu_fwd_into_);
   BLLM_OP("swiglu_bwd_lowrank(Tensor gu, Tensor base, Tensor u, Tensor P, float scale) -> Tensor", swiglu_bwd_lowrank);

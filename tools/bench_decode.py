@@ -34,7 +34,11 @@ Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 3
 cache, interleaved as above; ``--kv_arms fp8`` runs the fp8 arm alone (a batch whose bf16 cache
 does not fit).  One JSON line: ms per generated token per arm (``kv_model``, ``kv_fp8``), and each arm's
 cache bytes.
-Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 32768 --prompt 8192 --kv_dtype fp8"""
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 32768 --prompt 8192 --kv_dtype fp8
+
+``--ragged B,... --weight_dtype fp8`` (``--lora_rank R``: on a LoRA model): the decode steps on fp8
+weight packs (``ops.linear_w8``) against the model's own weights, interleaved (``ragged_weights``).
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128 --weight_dtype fp8"""
 import argparse
 import json
 import os
@@ -147,6 +151,48 @@ def ragged_sampling(a, m, cfg):
             json.dump(rows, f, indent=1)
 
 
+def ragged_weights(a, m, cfg):
+    """``--ragged B,... --weight_dtype fp8``: greedy ``generate_ragged`` on the model's weights
+    against the fp8 decode weights, interleaved: ``fp8`` builds the packs inside every call (what a
+    single ``generate_ragged`` call pays), ``fp8_prebuilt`` takes packs built once (what every
+    batch of ``generate_responses`` pays); ``pack_build_ms`` is that build."""
+    sizes = [int(b) for b in a.ragged.split(",")]
+    prompts, tok_name = _alpaca_prompts(a.model, cfg, max(sizes))
+    ctx = cfg.context_length
+    kv = None if a.kv_dtype == "model" else a.kv_dtype
+    m.new_decode_weights("fp8")                         # warm-up of the build
+    build = [_timed(lambda: m.new_decode_weights("fp8")) for _ in range(3)]
+    packs = m.new_decode_weights("fp8")
+    rows = []
+    for B in sizes:
+        ps = prompts[:B]
+        arms = {"model": lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv),
+                "fp8": lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv, weight_dtype="fp8"),
+                "fp8_prebuilt": lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv, weight_dtype=packs)}
+        for fn in arms.values():
+            fn()
+        times = {k: [] for k in arms}
+        for _ in range(a.repeats):
+            for k, fn in arms.items():
+                times[k].append(_timed(fn))
+        row = {"model": f"{a.model}-{a.num_params}", "lora_rank": a.lora_rank, "batch": B, "new_tokens": a.tokens,
+               "repeats": a.repeats, "tokenizer": tok_name, "kv_dtype": a.kv_dtype,
+               "graph": os.environ.get("BLLM_DECODE_GRAPH", "default"),
+               "pack_build_ms": round(1000 * statistics.median(build), 2)}
+        for k in arms:
+            ms = sorted(1000 * t / a.tokens for t in times[k])      # per step: all B rows advance together
+            row["weights_" + k] = {"ms_per_step": round(statistics.median(ms), 4),
+                                   "ms_per_step_range": [round(ms[0], 4), round(ms[-1], 4)]}
+        row["model_over_fp8_prebuilt"] = round(row["weights_model"]["ms_per_step"] /
+                                               row["weights_fp8_prebuilt"]["ms_per_step"], 3)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def context_bench(a, m, cfg):
     ctx = cfg.context_length
     if a.prompt + a.tokens > ctx:
@@ -251,15 +297,30 @@ def main():
     ap.add_argument("--kv_dtype", default="model", choices=["model", "fp8"],
                     help="--context: fp8 compares the KV-cache formats through generate_ragged (see above)")
     ap.add_argument("--kv_arms", default="model,fp8", help="--kv_dtype fp8: the arms to run")
+    ap.add_argument("--weight_dtype", default="model", choices=["model", "fp8"],
+                    help="--ragged: fp8 compares the decode steps on fp8 weight packs with the model's weights")
+    ap.add_argument("--lora_rank", type=int, default=0,
+                    help="--weight_dtype fp8: a LoRA model (this rank on every linear, nonzero B), folded into the packs")
     a = ap.parse_args()
     ops.load_ext(required=True)
     cfg = (get_config(a.model, a.num_params) if a.context is None
            else get_config(a.model, a.num_params, context_length=a.context)).replace(dtype=torch.bfloat16)
     torch.manual_seed(0)
     m = build_model(cfg, device="cuda")
+    if a.lora_rank > 0:
+        from building_llm_from_scratch_amd.models.lora import replace_linear_with_lora
+        for p in m.parameters():
+            p.requires_grad = False
+        replace_linear_with_lora(m, rank=a.lora_rank, alpha=2 * a.lora_rank, dtype=torch.bfloat16)
+        with torch.no_grad():
+            for n, p in m.named_parameters():
+                if n.endswith("lora.B"):
+                    p.normal_(0.0, 0.02)
     m.flatten()
     if a.graph is not None:
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
+    if a.ragged and a.weight_dtype == "fp8":
+        return ragged_weights(a, m, cfg)
     if a.ragged:
         return ragged_sampling(a, m, cfg) if a.temperature > 0 else ragged(a, m, cfg)
     if a.context is not None:
