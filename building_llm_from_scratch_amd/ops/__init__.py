@@ -400,6 +400,9 @@ def bias_grad_(dy, db, accumulate: bool = False):
 
 
 WGRAD_TILE, WGRAD_KGRAN = 256, 128
+# csrc/binding.cpp kMaxGemmPitch: the largest operand row pitch (elements) the MFMA GEMMs' 32-bit
+# per-lane staging offsets address exactly; the binding refuses anything above it
+GEMM_MAX_PITCH = 8_421_504
 
 
 # weight gradients on the token-major MFMA dW kernel (1.28-1.44 PF vs hipBLASLt's 0.96-1.17 on
@@ -421,6 +424,7 @@ def wgrad_gemm_ok(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> bool:
     return (M % WGRAD_TILE == 0 and N % WGRAD_TILE == 0 and K % WGRAD_KGRAN == 0 and K >= WGRAD_KGRAN
             and a.stride(1) == 1 and b.stride(1) == 1 and c.stride(1) == 1
             and a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0
+            and a.stride(0) <= GEMM_MAX_PITCH and b.stride(0) <= GEMM_MAX_PITCH
             and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
 
 
@@ -625,6 +629,7 @@ def gemm_nn_ok(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor] = Non
     ok = (M % WGRAD_TILE == 0 and N % WGRAD_TILE == 0 and K % WGRAD_KGRAN == 0 and K >= WGRAD_KGRAN
           and b.shape[0] == K and a.stride(1) == 1 and b.stride(1) == 1
           and a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0
+          and a.stride(0) <= GEMM_MAX_PITCH and b.stride(0) <= GEMM_MAX_PITCH
           and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
     return ok and (c is None or c.stride(1) == 1)
 
@@ -667,7 +672,8 @@ def gemm_nt_swiglu_ok(a: torch.Tensor, w: torch.Tensor) -> bool:
     return (w.shape[0] == 2 * F and w.shape[1] == K and M % 256 == 0 and F % 128 == 0 and K % 128 == 0
             and a.stride(1) == 1 and w.stride(1) == 1 and a.stride(0) % 8 == 0 and w.stride(0) % 8 == 0
             and a.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
-            and 256 * a.stride(0) * 2 < 2 ** 31 and 256 * w.stride(0) * 2 < 2 ** 31)
+            and 256 * a.stride(0) * 2 < 2 ** 31 and 256 * w.stride(0) * 2 < 2 ** 31
+            and (F + 128) * w.stride(0) * 2 < 2 ** 32)      # gemm_nt_swiglu_supported: w rows reach F + 127
 
 
 def gemm_nt_rope_ok(a: torch.Tensor, w: torch.Tensor, hd: int) -> bool:

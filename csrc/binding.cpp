@@ -502,10 +502,23 @@ void set_gemm_tile_maps(int64_t wg_map, int64_t wg_gm, int64_t nt_map, int64_t n
 
 // Operands of c [M, N] (+)= a^T b (TN: a [K, M], b [K, N]), a b (NN: a [M, K], b [K, N]) or a b^T
 // (NT: a [M, K], b [N, K]).  a and b: bf16/fp16 of one dtype, unit column stride, 16-B aligned base
-// and row pitch, pitch < 2^26 elements (the kernels' 32-bit tile offsets); c: unit column stride,
+// and row pitch, pitch <= kMaxGemmPitch elements; c: unit column stride,
 // base and pitch multiples of c_align bytes, dtype a's (c_dt 2), a's or fp32 (1) or any float dtype (0); dims < 2^31
 enum class Gemm { TN, NN, NT };
 struct GemmDims { int M, N, K; };
+// The LDS-DMA staging of the MFMA GEMMs adds a per-lane uint32_t BYTE offset
+// (row * ld + 8 * chunk) * 2 to a 64-bit wave-uniform base (csrc/gemm_wgrad.hip voffA / voffB, voA / voB;
+// csrc/gemm_nt.hip voA / voB).  It is exact while (rmax * ld + 8 * cmax) * 2 < 2^32, with
+//   wgrad_gemm_k, token-major operands (loaders are waves 0-3): rmax = (3*4+3)*2+1 = 31, cmax = 31
+//                                                               -> ld <= 69,273,658
+//   wgrad4_k:   rmax = 16*3 + 2*7 + 1 = 63, cmax = 31          -> ld <= 34,087,038
+//   wgrad_gemm_k<AK> (gemm_nn's A): rmax = (3*4+3)*16 + 15 = 255, cmax = 3
+//                                                               -> ld <= (2^31 - 24 - 1) / 255 = 8,421,504
+//   gemm_nt4p_k: *_supported asks 256 * ld * 2 < 2^31 on top of this (its rows reach 63, plus K * 2 bytes;
+//               the SwiGLU form's B rows reach F + 127: gemm_nt_swiglu_supported)
+// One bound for every operand, the minimum (the widest real pitch is 128,320): above it an offset
+// wraps mod 2^32 to a lower address that is still inside the tensor: wrong data, no fault.
+constexpr int64_t kMaxGemmPitch = 8421504;
 GemmDims gemm_operands(const Op& op, Gemm lay, const Tensor& a, const char* an, const Tensor& b, const char* bn,
                        const Tensor& c, const char* cn, int64_t c_align, int c_dt) {
   op.dims(a, 2, an);
@@ -515,8 +528,8 @@ GemmDims gemm_operands(const Op& op, Gemm lay, const Tensor& a, const char* an, 
   const int64_t N = b.size(lay == Gemm::NT ? 0 : 1);
   op.rows(a, -1, -1, a.scalar_type(), an);
   op.rows(b, lay == Gemm::NT ? N : K, lay == Gemm::NT ? K : N, a.scalar_type(), bn);
-  TORCH_CHECK(a.stride(0) < (int64_t(1) << 26) && b.stride(0) < (int64_t(1) << 26), op.name, ": row stride of ", an,
-              " / ", bn, " too large: ", a.stride(0), ", ", b.stride(0));
+  TORCH_CHECK(a.stride(0) <= kMaxGemmPitch && b.stride(0) <= kMaxGemmPitch, op.name, ": row stride of ", an, " / ",
+              bn, " too large: ", a.stride(0), ", ", b.stride(0), " (at most ", kMaxGemmPitch, " elements)");
   op.floating(c, cn);
   const bool own = c_dt == 0 || (c_dt == 1 && c.scalar_type() == at::kFloat);
   op.rows(c, M, N, own ? c.scalar_type() : a.scalar_type(), cn, false, c_align ? c_align : c.element_size());

@@ -381,6 +381,7 @@ __global__ __launch_bounds__(256) void rope_k(T* __restrict__ qkv, const float* 
                                               const int* __restrict__ pos_dev) {
   // one thread = 8 rotation pairs (two 16-B vectors of the head, 8 fp32 cos/sin each);
   // 32-bit index math (N * heads * chunks < 2^31 for every supported shape)
+  // NOTE: the host does not check this; ``total`` wraps past ~6.7e6 rows (Llama-3-8B heads), untested.
   static_assert(sizeof(T) == 2, "16-bit element types (fp32 uses rope_scalar_k)");
   const int half = hd / 2;
   if (pos_dev) {

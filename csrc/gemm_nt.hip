@@ -493,7 +493,10 @@ void gemm_nt2(DType dt, DType odt, const void* a, long lda, const void* b, long 
 }
 
 bool gemm_nt_swiglu_supported(int M, int F, int K, long lda, long ldb, long ldgu) {
-  return F > 0 && F % 128 == 0 && gemm_nt2_supported(M, 2 * F, K, lda, ldb) && ldgu % 8 == 0;
+  // a wave's staged B rows reach F + 127 rows past its base (the up half of the gate / up image, voB):
+  // (F + 127) * ldb * 2 + the K-tile advance (< ldb * 2) must stay a 32-bit buffer offset
+  return F > 0 && F % 128 == 0 && gemm_nt2_supported(M, 2 * F, K, lda, ldb) && ldgu % 8 == 0 &&
+         (long)(F + 128) * ldb * 2 < (1L << 32);
 }
 
 void gemm_nt_swiglu(DType dt, const void* a, long lda, const void* w, long ldw, void* gu, long ldgu, void* act, int M,

@@ -322,6 +322,54 @@ def test_gemms():
              (2, wider(C))))
 
 
+def test_gemm_operand_pitch_bound():
+    """Row pitches 8 elements above ``kMaxGemmPitch`` (csrc/binding.cpp: the largest pitch whose
+    32-bit per-lane staging offsets are exact) are refused for either operand of every layout; a
+    refused call launches nothing, so the wide allocations stay uninitialised.  The accepted side,
+    8 elements below the bound, is tests/test_large_extent_gpu.py."""
+    from large_extent_shapes import GEMM_MAX_PITCH, GEMM_NT_PITCH_LIMIT, GIB
+    if torch.cuda.mem_get_info()[0] < 10 * GIB:
+        pytest.skip("needs 8 GiB of free device memory (+ 2 GiB)")
+    M, Nn, K = 256, 256, 128
+    over = GEMM_MAX_PITCH + 8
+    wide_k = torch.empty(K, over, dtype=DT, device=DEV)[:, :256]      # [128, 256] rows ``over`` apart: TN a / b, NN b
+    a, b, c = rnd(K, M), rnd(K, Nn), torch.zeros(M, Nn, device=DEV)
+    refusals("wgrad_gemm_", (a, b, c, False, 1), ((0, wide_k), (1, wide_k)))
+    a2, b2 = rnd(2 * K, M), rnd(2 * K, Nn)
+    wide_2k = torch.empty(2 * K, over, dtype=DT, device=DEV)[:, :256]
+    refusals("wgrad_gemm_tail_", (a2, b2, c, False, 0, 2), ((0, wide_2k), (1, wide_2k)))
+    del wide_2k
+    torch.cuda.empty_cache()
+    an, bt = rnd(M, K), rnd(Nn, K)
+    wide_m = torch.empty(M, over, dtype=DT, device=DEV)[:, :K]        # [256, 128] rows ``over`` apart: NN / NT a, NT b
+    refusals("gemm_nn_", (an, b, c, False), ((0, wide_m), (1, wide_k)))
+    refusals("gemm_nt_", (an, bt, c, False), ((0, wide_m), (1, wide_m)))
+    assert wide_k.stride(0) == wide_m.stride(0) == over
+    assert "too large" in _message("gemm_nn_", (wide_m, b, c, False))      # refused by the pitch check itself
+    assert "too large" in _message("wgrad_gemm_", (a, wide_k, c, False, 1))
+    # the planners of ops/__init__.py agree with the binding
+    assert ops.wgrad_gemm_ok(a, b, c) and not ops.wgrad_gemm_ok(wide_k, b, c) and not ops.wgrad_gemm_ok(a, wide_k, c)
+    assert ops.gemm_nn_ok(an, b, c) and not ops.gemm_nn_ok(wide_m, b, c) and not ops.gemm_nn_ok(an, wide_k, c)
+    assert ops.GEMM_MAX_PITCH == GEMM_MAX_PITCH
+    del wide_k, wide_m
+    torch.cuda.empty_cache()
+    # gemm_nt_swiglu_: a wave stages w rows up to F + 127 past its base, so the pitch that
+    # gemm_nt_'s own guard (256 rows) accepts is refused once (F + 128) * pitch * 2 reaches 2^32
+    F, pitch = 512, GEMM_NT_PITCH_LIMIT - 8
+    assert 256 * pitch * 2 < 1 << 31 and (F + 128) * pitch * 2 >= 1 << 32
+    w = torch.empty(2 * F, pitch, dtype=DT, device=DEV)[:, :K]
+    gu, act = torch.zeros(M, 2 * F, dtype=DT, device=DEV), torch.zeros(M, F, dtype=DT, device=DEV)
+    call("gemm_nt_swiglu_", (an, rnd(2 * F, K), gu, act))                  # the same shapes, dense w: accepted
+    refusals("gemm_nt_swiglu_", (an, rnd(2 * F, K), gu, act), ((1, w),))
+    assert ops.gemm_nt_swiglu_ok(an, rnd(2 * F, K)) and ops.gemm_nt_ok(an, w) and not ops.gemm_nt_swiglu_ok(an, w)
+
+
+def _message(name, args):
+    with pytest.raises(RuntimeError) as e:
+        call(name, args)
+    return str(e.value)
+
+
 # ------------------------------------------------------------------ attention
 def test_attn_decode():
     q, kc, vc = rnd(1, H, HD), rnd(1, G, T, HD), rnd(1, G, T, HD)
