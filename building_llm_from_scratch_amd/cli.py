@@ -51,6 +51,13 @@ def perform_checks(args):
         raise ValueError("--generate_kv_dtype must be 'model' or 'fp8'.")
     if getattr(args, "generate_weight_dtype", "model") not in ("model", "fp8"):
         raise ValueError("--generate_weight_dtype must be 'model' or 'fp8'.")
+    spec = getattr(args, "generate_speculative", 0)
+    if not 0 <= spec <= 7:
+        raise ValueError("--generate_speculative must be in 0..7 (0: off).")
+    if spec and (getattr(args, "generate_kv_dtype", "model") == "fp8"
+                 or getattr(args, "generate_weight_dtype", "model") == "fp8"):
+        raise ValueError("--generate_speculative runs on the default cache and weights: not with "
+                         "--generate_kv_dtype fp8 or --generate_weight_dtype fp8.")
     if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -188,6 +195,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "every projection on e4m3 packs with one fp32 scale per output channel, LoRA folded in, built "
                         "once per run of the prompts (extra memory, about half the 16-bit weights; the first token "
                         "of an answer still comes from the exact weights; answers can differ)")
+    x.add_argument("--generate_speculative", type=int, default=0,
+                   help="exact speculative decoding of --generate_prompts: K drafts per step (1..7) by prompt lookup, "
+                        "the continuation of the latest earlier occurrence of the answer's last two tokens in its own "
+                        "text; verified with the seeded sampler, so the answers are those of 0 (off) in fewer steps "
+                        "where an answer quotes its prompt or repeats itself.  Needs K more free positions per prompt")
     x.add_argument("--generate_only", action="store_true",
                    help="no data preparation, training or final save: build the model (--load_weights / "
                         "--resume), answer --generate_prompts, exit")
@@ -277,6 +289,8 @@ def _generate_responses(trainer, args, rank, out_dir):
         sampling["kv_dtype"] = "fp8"
     if getattr(args, "generate_weight_dtype", "model") == "fp8":
         sampling["weight_dtype"] = "fp8"
+    if getattr(args, "generate_speculative", 0):
+        sampling["speculative"] = args.generate_speculative
     responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size, **sampling)
     if rank != 0:
         return

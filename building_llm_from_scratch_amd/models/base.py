@@ -686,7 +686,8 @@ class BaseLM(nn.Module):
                              comps[-1].head.w8_pack())
 
     @torch.no_grad()
-    def forward_cached_rows(self, idx: torch.Tensor, cache, pos_rows: torch.Tensor, weights=None) -> torch.Tensor:
+    def forward_cached_rows(self, idx: torch.Tensor, cache, pos_rows: torch.Tensor, weights=None,
+                            q_per_row: int = 1) -> torch.Tensor:
         """:meth:`forward_cached_dev` with a position per row: one decode token per row (idx [B, 1]),
         row b at ``pos_rows[b]`` (int32 [B] on the device, each below the cache length and the
         model's context length -- the caller's entry check, train/generate.py:generate_ragged).
@@ -694,8 +695,29 @@ class BaseLM(nn.Module):
 
         ``weights`` (:meth:`new_decode_weights`): every projection of the step, the head's
         included, runs on its fp8 pack (``ops.linear_w8``) instead of the model's weights; norms,
-        embeddings, RoPE and attention are unchanged.  ``None``: exactly the step above."""
+        embeddings, RoPE and attention are unchanged.  ``None``: exactly the step above.
+
+        ``q_per_row=Q > 1`` (the verify step of speculative decoding): Q consecutive tokens per
+        batch row.  ``idx`` is [B*Q, 1] and ``pos_rows`` int32 [B*Q], row b*Q + j = token j of batch
+        row b at position ``pos_rows[b*Q] + j`` (the caller fills it so, and keeps
+        ``pos_rows[b*Q] + Q`` inside the cache).  Embedding, RoPE, norms, projections and MLP run per
+        row as they are; attention is ``ops.attn_extend_rows`` (the Q keys / values appended, query
+        j over keys 0..pos+j); the head returns all B*Q logits rows.  Not with ``weights`` or an
+        fp8 cache (ValueError)."""
         comps = self._comps
+        Q = int(q_per_row)
+        if Q != 1:
+            if Q < 1 or idx.shape[0] % Q or pos_rows.numel() != idx.shape[0]:
+                raise ValueError(f"forward_cached_rows: q_per_row ({q_per_row}) must be >= 1 and divide the "
+                                 f"{idx.shape[0]} rows of idx, with one position per row")
+            if weights is not None or len(cache[0]) != 2 or cache[0][0].dtype == torch.float8_e4m3fn:
+                raise ValueError("forward_cached_rows: q_per_row > 1 runs on the model's own weights and a cache "
+                                 "in the parameter dtype (no weights=, no fp8 cache)")
+            pos_b = pos_rows[::Q].contiguous()          # the batch rows' positions, for attention
+            x = comps[0].infer_rows(idx, pos_rows)
+            for c, kv in zip(comps[1:-1], cache):
+                x = c.infer_rows(x, pos_rows, kv, q_per_row=Q, pos_b=pos_b)
+            return comps[-1].infer(x, idx.shape[0], 1)
         x = comps[0].infer_rows(idx, pos_rows)
         if weights is not None:
             if not isinstance(weights, DecodeWeights) or len(weights.blocks) != len(comps) - 2:

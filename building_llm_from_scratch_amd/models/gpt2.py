@@ -190,15 +190,20 @@ class GPTBlockCompute(UnitCompute):
         m, _ = self.proj.forward(ops.gelu_fwd(f))
         return x2 + m
 
-    def infer_rows(self, x2d, pos_rows, kv, weights=None):
+    def infer_rows(self, x2d, pos_rows, kv, weights=None, q_per_row: int = 1, pos_b=None):
         """``infer_dev`` with a position per row (int32 [B] on the device).  ``weights``: the
-        block's fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``."""
+        block's fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``.
+        ``q_per_row=Q > 1``: Q consecutive tokens per batch row (rows b*Q + j, ``pos_b`` int32 [B]
+        = the batch rows' positions ``pos_rows[::Q]``); attention is ``ops.attn_extend_rows``."""
         H = self.rctx.cfg.n_heads
         h1 = self._ln(x2d, self.block.norm1)[0]
         if weights is not None:
             qkv = self.qkv.forward_w8(h1, weights[0])
         else:
             qkv, _ = self.qkv.forward(h1)
+        if q_per_row != 1:
+            return self._infer_out(x2d, ops.attn_extend_rows(qkv, kv[0], kv[1], pos_b, q_per_row, H, H,
+                                                             pos_rows=pos_rows), weights)
         return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, H, scales=kv[2:]),
                                weights)
 

@@ -292,15 +292,20 @@ class LlamaBlockCompute(UnitCompute):
         x3, _ = self.down.forward(ops.swiglu_fwd(gu), residual=x2)
         return x3
 
-    def infer_rows(self, x2d, pos_rows, kv, weights=None):
+    def infer_rows(self, x2d, pos_rows, kv, weights=None, q_per_row: int = 1, pos_b=None):
         """``infer_dev`` with a position per row (int32 [B] on the device): RoPE rotates row b at
         ``pos_rows[b]`` and the decode kernel appends and attends there.  ``weights``: the block's
-        fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``."""
+        fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``.
+        ``q_per_row=Q > 1``: Q consecutive tokens per batch row (rows b*Q + j, ``pos_b`` int32 [B]
+        = the batch rows' positions ``pos_rows[::Q]``); attention is ``ops.attn_extend_rows``."""
         cfg = self.rctx.cfg
         H, G, hd = cfg.n_heads, cfg.n_kv_groups, cfg.head_dim
         cos, sin = self.rctx.rope
         qkv = self._infer_qkv(x2d, weights)
         ops.rope_pos_(qkv, cos, sin, pos_rows, H, G, hd)
+        if q_per_row != 1:
+            return self._infer_out(x2d, ops.attn_extend_rows(qkv, kv[0], kv[1], pos_b, q_per_row, H, G,
+                                                             pos_rows=pos_rows), weights)
         return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G, scales=kv[2:]),
                                weights)
 

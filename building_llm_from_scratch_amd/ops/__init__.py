@@ -26,7 +26,7 @@ __all__ = [
     "flash_attn_varlen_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
     "swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank_wgrad_ok",
     "gelu_fwd", "gelu_bwd", "gelu_bwd_bias", "gelu_bwd_act", "dropout_bwd_bias", "ce_fwd", "ce_bwd_", "embedding_fwd", "embedding_bwd",
-    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "kv_cache_fill_varlen", "kv_quantize_rows", "kv_dequantize", "bias_grad_", "ext_available", "load_ext", "attention_backend",
+    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "attn_extend_rows", "spec_advance", "kv_cache_fill_varlen", "kv_quantize_rows", "kv_dequantize", "bias_grad_", "ext_available", "load_ext", "attention_backend",
     "lora_down", "lora_up_", "lora_wgrad", "lora_pack_t", "lora_kernel_ok", "lora_kernel_ok_dims",
     "lora_down_into", "lora_block_", "rmsnorm_fwd_into", "swiglu_fwd_into", "sum_partials_",
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
@@ -46,7 +46,8 @@ def _hip(t: torch.Tensor) -> bool:
 
 DEBUG_CODES = {1: "embedding token id outside [0, vocab)", 2: "cross-entropy target outside [0, V)",
                3: "decode cache position outside [0, Tmax)", 4: "rope device position negative",
-               5: "sampler row counter outside [0, out.size(1))"}
+               5: "sampler row counter outside [0, out.size(1))",
+               6: "speculative step state (row counter, position or corpus length) out of range"}
 
 
 class _CheckedOps:
@@ -338,6 +339,53 @@ def attn_decode_append_rows(qkv, kc, vc, pos, H: int, G: int, scales=None):
             return _k().attn_decode_append_split(qkv, kc, vc, pos, H, G)
         return _k().attn_decode_append_rows(qkv, kc, vc, pos, H, G)
     return ref.attn_decode_append_rows(qkv, kc, vc, pos, H, G)
+
+
+EXTEND_MAX_Q = 8        # tokens per row of the attn_extend_rows kernel ...
+EXTEND_MAX_QUERIES = 32   # ... and query vectors per kv group (Q * H / G): one MFMA tile
+
+
+def attn_extend_rows(qkv, kc, vc, pos, Q: int, H: int, G: int, pos_rows=None):
+    """Q new tokens per row over the cache: ``qkv`` [B*Q, (H+2G)*hd] (RoPE applied), row b*Q + j =
+    token j of batch row b at position ``pos[b] + j`` (``pos`` int32 [B] on qkv's device, every
+    ``pos[b] + Q <= Tmax``).  The K / V of the Q tokens go into cache rows pos[b] .. pos[b]+Q-1 and
+    query j attends over keys 0 .. pos[b]+j -> [B*Q, H*hd]: what Q consecutive
+    ``attn_decode_append_rows`` calls at pos, pos + 1, ... give (``ops.reference.attn_extend_rows``).
+
+    bf16 / fp16 with head dim 64 / 128, ``2 <= Q <= 8`` and ``Q * (H / G) <= 32`` run the HIP kernel
+    (csrc/attn_extend.hip: split-KV at every cache length, scores and P V on MFMA, no host read:
+    graph-capturable); ``Q == 1`` is ``attn_decode_append_rows``; CPU tensors, fp32, other head
+    dims and more query vectors per kv group go to the oracle.  ``pos_rows`` (int32 [B*Q], the
+    vector pos[b] + j, which a model has for RoPE anyway) saves forming it here."""
+    Q = int(Q)
+    if Q < 1 or qkv.shape[0] != kc.shape[0] * Q:
+        raise ValueError(f"attn_extend_rows: qkv must have B * Q = {kc.shape[0]} * {Q} rows, got {qkv.shape[0]}")
+    if Q == 1:
+        return attn_decode_append_rows(qkv, kc, vc, pos, H, G)
+    if _decode_kernel(qkv, kc.shape[3]) and Q <= EXTEND_MAX_Q and G > 0 and H % G == 0 \
+            and Q * (H // G) <= EXTEND_MAX_QUERIES:
+        load_ext(required=True)
+        if pos_rows is None:
+            pos_rows = (pos[:, None] + torch.arange(Q, dtype=torch.int32, device=pos.device)).reshape(-1)
+        return _k().attn_extend_rows(qkv, kc, vc, pos, pos_rows, Q, H, G)
+    return ref.attn_extend_rows(qkv, kc, vc, pos, Q, H, G)
+
+
+def spec_advance(idx, samp, hist, h0, pos, ctr, nsteps, finished, out, eos_id: int = -1, ngram: int = 2,
+                 accept: bool = True):
+    """One step of speculative decoding's device-side bookkeeping, in place (the contract is
+    ``ops.reference.spec_advance``): accept the drafts in ``idx[:, 1:]`` that ``samp`` confirms
+    (tokens to ``out`` and ``hist``; ``pos``, ``ctr``, ``nsteps``, ``finished`` updated), then write
+    the next step's input tokens into ``idx``: the last emitted token and Q - 1 prompt-lookup
+    drafts.  ``accept=False``: only the draft part.  GPU tensors run the HIP kernel (csrc/spec.hip,
+    one workgroup per row, no host read), CPU tensors the oracle."""
+    if not 1 <= int(ngram) <= 4 or idx.dim() != 2 or not 1 <= idx.shape[1] <= 8:
+        raise ValueError(f"spec_advance: ngram must be in 1..4 and idx [B, Q <= 8], got ngram {ngram}, idx "
+                         f"{tuple(idx.shape)}")
+    if _hip(idx):
+        _k().spec_advance_(idx, samp, hist, h0, pos, ctr, nsteps, finished, out, int(eos_id), int(ngram), bool(accept))
+        return
+    ref.spec_advance(idx, samp, hist, h0, pos, ctr, nsteps, finished, out, int(eos_id), int(ngram), bool(accept))
 
 
 def sample_rows(logits, stream, ctr, seed: int, temperature: float, top_k: int = 0, top_p: float = 1.0,

@@ -553,6 +553,82 @@ def attn_decode_append_rows(qkv, kcache, vcache, pos, H: int, G: int):
     return out
 
 
+def attn_extend_rows(qkv, kcache, vcache, pos, Q: int, H: int, G: int):
+    """Reference for Q tokens per row over the cache: qkv [B*Q, (H+2G)*hd], row b*Q + j = token j of
+    batch row b at position pos[b] + j.  By definition Q consecutive per-row decode steps at
+    ``pos``, ``pos + 1``, ...: token j's k / v go into cache row pos[b] + j and its query attends
+    over keys 0..pos[b]+j -> [B*Q, H*hd]."""
+    B = kcache.shape[0]
+    rows = qkv.view(B, Q, -1)
+    out = torch.empty(B, Q, H * kcache.shape[3], dtype=qkv.dtype, device=qkv.device)
+    for j in range(Q):
+        out[:, j] = attn_decode_append_rows(rows[:, j].contiguous(), kcache, vcache, pos + j, H, G)
+    return out.view(B * Q, -1)
+
+
+def spec_advance(idx, samp, hist, h0, pos, ctr, nsteps, finished, out, eos_id: int, ngram: int,
+                 accept: bool = True):
+    """One step of speculative decoding's bookkeeping (prompt lookup), in place; ``K = Q - 1``.
+
+    ``idx`` int64 [B, Q]: the step's input tokens (the last emitted token, then K drafts);
+    ``samp`` int64 [B, Q]: what the sampler chose from the step's Q logits rows; ``hist`` int32
+    [B, Lh]: corpus row b = ``h0[b]`` hint tokens, then the row's sequence (position p at
+    ``hist[b, h0[b] + p]``); ``h0`` / ``pos`` / ``ctr`` / ``nsteps`` int32 [B]; ``finished`` bool
+    [B]; ``out`` int64 [B, new].
+
+    Accept (``accept``, rows that are not finished): a = the number of leading j in 1..K with
+    ``idx[b, j] == samp[b, j - 1]``; e = min(a + 1, new - ctr[b]), cut to j + 1 at the first
+    ``samp[b, j] == eos_id`` with j < e (``eos_id >= 0``), which finishes the row; ``samp[b, :e]``
+    goes to ``out[b, ctr[b]:ctr[b] + e]`` and to ``hist`` at positions pos[b] + 1 ..; pos and ctr
+    advance by e, nsteps by 1; the row finishes when ctr reaches new.  A finished row changes
+    nothing.
+
+    Draft (every row): n = h0[b] + pos[b] + 1, c = hist[b, :n].  With the largest i in
+    [0, n - ngram - 1] such that c[i : i + ngram] == c[n - ngram : n] and per = n - i - ngram,
+    draft j = c[i + ngram + ((j - 1) mod per)]; without one (or n <= ngram) every draft is c[n - 1].
+    ``idx[b] = [c[n - 1], draft 1, ..., draft K]``."""
+    B, Q = idx.shape
+    K, new = Q - 1, out.shape[1]
+    for b in range(B):
+        if accept and not bool(finished[b]):
+            s = [int(v) for v in samp[b].tolist()]
+            d = [int(v) for v in idx[b].tolist()]
+            a = 0
+            while a < K and d[a + 1] == s[a]:
+                a += 1
+            c, p = int(ctr[b]), int(pos[b])
+            e = min(a + 1, new - c)
+            fin = False
+            if eos_id >= 0:
+                for j in range(e):
+                    if s[j] == eos_id:
+                        e, fin = j + 1, True
+                        break
+            for j in range(e):
+                out[b, c + j] = s[j]
+                hist[b, int(h0[b]) + p + 1 + j] = s[j]
+            pos[b] += e
+            ctr[b] += e
+            nsteps[b] += 1
+            if fin or c + e >= new:
+                finished[b] = True
+        n = int(h0[b]) + int(pos[b]) + 1
+        c = [int(v) for v in hist[b, :n].tolist()]
+        best = -1
+        if n > ngram:
+            tail = c[n - ngram:]
+            for i in range(n - ngram - 1, -1, -1):
+                if c[i:i + ngram] == tail:
+                    best = i
+                    break
+        row = [c[n - 1]] * Q
+        if best >= 0:
+            per = n - best - ngram
+            for j in range(1, Q):
+                row[j] = c[best + ngram + (j - 1) % per]
+        idx[b] = torch.tensor(row, dtype=idx.dtype, device=idx.device)
+
+
 def kv_cache_fill_varlen(qkv, cu, kcache, vcache):
     """Reference for the cache prefill from a packed batch: sequence b is rows [cu[b], cu[b+1]) of
     qkv [N, (H+2G)*hd]; cache rows (b, g, t < len_b) <- the k / v of row cu[b] + t."""

@@ -30,6 +30,11 @@ Same contract: sliding window of ``context_size`` tokens, optional top-k thresho
   ``ops.sample_rows`` (csrc/sample.hip): temperature, top-k, top-p and a counter-based random
   stream per row, so a row's tokens depend on (seed, its stream id, its logits) and not on the
   batch it sits in.  In :func:`generate_ragged` the sampler is part of the captured step.
+* ``speculative=K`` (:func:`generate_ragged`): exact speculative decoding.  A step feeds every row
+  its last token and K prompt-lookup drafts (``forward_cached_rows(..., q_per_row=K + 1)``,
+  ``ops.attn_extend_rows``), samples all K + 1 logits rows with the counters the plain loop would
+  use and keeps the drafts the sampler confirms (``ops.spec_advance``): the plain loop's tokens in
+  fewer steps, one graph replay per step (:class:`SpecDecodeGraph`).
 """
 from __future__ import annotations
 
@@ -225,12 +230,99 @@ class RowsDecodeGraph:
         return self.logits
 
 
+SPEC_NGRAM = 2      # n-gram length of the prompt-lookup drafts (ops.spec_advance)
+SPEC_MAX_DRAFTS = 7  # drafts per step: the verify step's 1 + K tokens per row fit ops.attn_extend_rows
+
+
+class SpecDecodeGraph:
+    """One verify step of speculative decoding (:func:`generate_ragged`, ``speculative=K``), sibling
+    of :class:`RowsDecodeGraph`: every row feeds Q = K + 1 tokens (its last emitted token and K
+    drafts, ``idx`` int64 [B, Q]) at positions ``pos[b] ..``, and the step is
+
+    * the position and counter vectors of the B*Q rows, ``pos[b] + j`` and ``ctr[b] + j``,
+    * ``forward_cached_rows(..., q_per_row=Q)`` -> logits [B*Q, V],
+    * ``ops.sample_rows`` on them with the row's stream and those counters: ``samp[b, j]`` is the
+      token the plain loop would draw as the row's token number ``ctr[b] + j`` from these logits,
+    * ``ops.spec_advance``: accept the confirmed drafts (tokens to ``out`` and ``hist``; ``pos``,
+      ``ctr``, ``nsteps``, ``finished`` advance) and draft the next step's ``idx``.
+
+    Everything lives on the device, so with ``capture`` the step is one HIP graph and
+    :meth:`replay` one launch; without it the same calls run eagerly.  The warm-up passes run the
+    forward alone with every row at the cache's last Q slots, which any later step overwrites
+    before it reads them (the entry check of ``generate_ragged`` keeps the prompts below them)."""
+
+    def __init__(self, model, cache, idx, hist, h0, pos, ctr, nsteps, finished, out, stream, seed: int,
+                 temperature: float, top_k: int, top_p: float, eos_id: int, capture: bool = True):
+        from .. import ops
+        B, Q = idx.shape
+        device = idx.device
+        Tmax = cache[0][0].shape[2]
+        j = torch.arange(Q, dtype=torch.int32, device=device)
+        stream_rows = stream.repeat_interleave(Q)
+
+        def step():
+            pos_rows = (pos[:, None] + j).reshape(-1)
+            ctr_rows = (ctr[:, None] + j).reshape(-1)
+            logits = model.forward_cached_rows(idx.view(B * Q, 1), cache, pos_rows, q_per_row=Q)
+            samp = ops.sample_rows(logits.contiguous(), stream_rows, ctr_rows, seed, temperature, top_k, top_p)
+            ops.spec_advance(idx, samp.view(B, Q), hist, h0, pos, ctr, nsteps, finished, out, eos_id, SPEC_NGRAM)
+            return logits
+
+        self._step = step
+        self.graph = None
+        self.logits = None
+        if not capture:
+            return
+        warm = torch.full((B * Q,), Tmax - Q, dtype=torch.int32, device=device) + j.repeat(B)
+        cur = torch.cuda.current_stream(device)
+        side = torch.cuda.Stream(device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                model.forward_cached_rows(idx.view(B * Q, 1), cache, warm, q_per_row=Q)
+        cur.wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            self.logits = step()
+
+    def replay(self) -> None:
+        """One verify step: reads and rewrites the state tensors given at construction."""
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self.logits = self._step()
+
+
+def _spec_args(K, B: int, temperature, seed, kv_dtype, weight_dtype, draft_hints):
+    """Entry check of ``generate_ragged``'s speculative arguments -> K (0: off)."""
+    if K is None:
+        if draft_hints is not None:
+            raise ValueError("generate_ragged: draft_hints belong to speculative decoding; pass speculative=K")
+        return 0
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= SPEC_MAX_DRAFTS:
+        raise ValueError(f"generate_ragged: speculative must be None or an int in 1..{SPEC_MAX_DRAFTS}, got {K!r}")
+    if seed is None and float(temperature) != 0.0:
+        raise ValueError("generate_ragged: speculative decoding verifies drafts with the seeded device sampler; "
+                         "pass seed=... or temperature=0 (one multinomial over the batch cannot be verified)")
+    if kv_dtype is not None or weight_dtype is not None:
+        raise ValueError("generate_ragged: speculative decoding runs on the default cache and weights "
+                         "(no kv_dtype / weight_dtype)")
+    if draft_hints is not None:
+        if not isinstance(draft_hints, (list, tuple)) or len(draft_hints) != B:
+            raise ValueError(f"generate_ragged: draft_hints must hold one entry per prompt ({B})")
+        for b, h in enumerate(draft_hints):
+            if h is not None and (not isinstance(h, torch.Tensor) or h.dim() != 1 or h.dtype != torch.long):
+                raise ValueError(f"generate_ragged: draft hint {b} must be None or a 1-D LongTensor")
+    return K
+
+
 @torch.no_grad()
 def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temperature: float = 0.0,
                     top_k: Optional[int] = None, eos_id: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
                     seed: Optional[int] = None, streams=None, kv_dtype: Optional[str] = None,
-                    weight_dtype=None) -> list:
+                    weight_dtype=None, speculative: Optional[int] = None, draft_hints=None,
+                    stats: Optional[dict] = None) -> list:
     """Batched KV-cache generation from prompts of different lengths.
 
     ``prompts``: a non-empty list of non-empty 1-D LongTensors.  Returns one 1-D tensor per prompt:
@@ -273,7 +365,23 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     built already (``model.new_decode_weights()``) is taken as it is.  The prefill runs on the
     model's own weights, so the first new token comes from exact logits; every later one from the
     quantised weights, so the tokens can differ from the default's.  The packs are extra memory,
-    about half the bytes of 16-bit weights.  None: the model's weights, as before."""
+    about half the bytes of 16-bit weights.  None: the model's weights, as before.
+
+    ``speculative=K`` (1..7): exact speculative decoding with prompt-lookup drafts.  After the
+    first token every step feeds each row its last token and K drafts -- the continuation of the
+    latest earlier occurrence of the row's trailing ``SPEC_NGRAM`` tokens in its own text, or in
+    ``draft_hints[b]`` (a 1-D LongTensor or None per prompt, searched as if it stood ahead of the
+    prompt) -- through one ``forward_cached_rows(..., q_per_row=K + 1)``, runs the device sampler
+    on all K + 1 logits rows with the counters the plain loop would use, and keeps the drafts the
+    sampler confirms plus one more token (:class:`SpecDecodeGraph`; one graph replay per step, the
+    host reads the finished mask every ``EOS_CHECK_EVERY`` steps).  A row's token number c is a
+    function of (seed, stream, c, logits) either way, so the answers are those of
+    ``speculative=None`` up to GEMM rounding of the logits; drafts and hints change the number
+    of steps, never the tokens.  It needs the device sampler (``seed``, or ``temperature == 0``:
+    greedy through ``sample_rows``), the default cache and weights, and
+    ``max(len) + max_new_tokens + K <= context_size``: a verify step writes K cache rows past the
+    position.  ``stats`` (a dict) receives ``steps`` (verify steps per prompt) and ``new_tokens``
+    (tokens drawn per prompt, an eos included)."""
     from .. import ops
     from ..models.base import DecodeWeights, pack_prompts
     if kv_dtype not in (None, "fp8"):
@@ -288,15 +396,24 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
             raise ValueError(f"generate_ragged: prompt {b} must be a non-empty 1-D LongTensor")
     lens = [int(p.numel()) for p in prompts]
     new = max(int(max_new_tokens), 0)
+    K = _spec_args(speculative, len(prompts), temperature, seed, kv_dtype, weight_dtype, draft_hints)
+    if K and max(lens) + new + K > context_size:
+        raise ValueError(f"generate_ragged: the longest prompt ({max(lens)} tokens) + max_new_tokens ({new}) + "
+                         f"speculative ({K}) exceeds context_size ({context_size}): a verify step writes K cache "
+                         f"rows past the position")
     if max(lens) + new > context_size:
         raise ValueError(f"generate_ragged: the longest prompt ({max(lens)} tokens) + max_new_tokens ({new}) "
                          f"exceeds context_size ({context_size}); this path has no sliding window")
     if context_size > model.cfg.context_length:
         raise ValueError(f"generate_ragged: context_size ({context_size}) exceeds the model's context length "
                          f"({model.cfg.context_length})")
+    if K and seed is None:      # greedy through the device sampler: at temperature 0 it is the argmax
+        seed, top_k, top_p = 0, None, None
     sampler = _sampler_args("generate_ragged", len(prompts), temperature, top_k, top_p, seed, streams)
     device = next(model.parameters()).device
     if new == 0:
+        if stats is not None:
+            stats["steps"], stats["new_tokens"] = [0] * len(prompts), [0] * len(prompts)
         return [p.to(device) for p in prompts]
     was_training = model.training
     model.eval()
@@ -328,10 +445,13 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
             nxt = torch.zeros(B, 1, dtype=torch.long, device=device)
             draw(logits, nxt)
             n = 1
-            if new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
+            if K:
+                n = _speculate(model, cache, prompts, lens, draft_hints, K, nxt, pos, ctr, finished, out, stream_t,
+                               seed, temperature, sampler, eos, stats)
+            if not K and new > 8 and _graph_enabled() and model.decode_graph_ok(cache):
                 dec = RowsDecodeGraph(model, cache, pos, device, sampler=draw, **kw)
                 dec.idx.copy_(nxt)
-            while n < new:
+            while not K and n < new:
                 if eos_id is not None and n - checked >= EOS_CHECK_EVERY:
                     if bool(finished.all()):   # tokens after a row's first eos are dropped below
                         break
@@ -371,6 +491,51 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
         keep = [n] * B
     model.train(was_training)
     return [torch.cat((idx[seq.bounds[b]:seq.bounds[b + 1]], gen[b, :keep[b]])) for b in range(B)]
+
+
+def spec_state(prompts, lens, hints, Q: int, new: int, first, pos):
+    """The device-side state of the speculative loop after the first token (``first`` [B, 1] at
+    positions ``pos``, int32 [B] on the device) -> (idx int64 [B, Q] zeros, hist int32 [B, Lh],
+    h0 int32 [B], nsteps int32 [B] zeros).  Corpus row b: its hint, its prompt, the first token,
+    and room for the answer and one step's tokens."""
+    B, device = len(prompts), first.device
+    hints = [None] * B if hints is None else hints
+    hl = [0 if h is None else int(h.numel()) for h in hints]
+    Lh = max(h + n for h, n in zip(hl, lens)) + new + Q
+    host = torch.zeros(B, Lh, dtype=torch.int32)
+    for b in range(B):
+        if hl[b]:
+            host[b, :hl[b]] = hints[b].to("cpu", torch.int32)
+        host[b, hl[b]:hl[b] + lens[b]] = prompts[b].to("cpu", torch.int32)
+    hist = host.to(device)
+    h0 = torch.tensor(hl, dtype=torch.int32).to(device)
+    # pos[b]: the position of the row's last emitted token, which is the next step's first input
+    hist[torch.arange(B, device=device), (h0 + pos).to(torch.long)] = first[:, 0].to(torch.int32)
+    return (torch.zeros(B, Q, dtype=torch.long, device=device), hist, h0,
+            torch.zeros(B, dtype=torch.int32, device=device))
+
+
+def _speculate(model, cache, prompts, lens, hints, K: int, first, pos, ctr, finished, out, stream_t, seed,
+               temperature, sampler, eos: int, stats) -> int:
+    """The speculative decode loop of :func:`generate_ragged` after the first token (``first``
+    [B, 1], already in ``out[:, 0]``, ``ctr`` = 1): builds the rows' corpora, drafts, and runs at
+    most ``new - 1`` verify steps.  Returns the number of valid columns of ``out`` (all of them:
+    every row ends finished or with ``new`` tokens)."""
+    from .. import ops
+    new = out.shape[1]
+    idx, hist, h0, nsteps = spec_state(prompts, lens, hints, K + 1, new, first, pos)
+    finished |= ctr >= new                      # new == 1: the first token was the answer
+    ops.spec_advance(idx, idx.clone(), hist, h0, pos, ctr, nsteps, finished, out, eos, SPEC_NGRAM, accept=False)
+    capture = new > 8 and _graph_enabled() and model.decode_graph_ok(cache)
+    dec = SpecDecodeGraph(model, cache, idx, hist, h0, pos, ctr, nsteps, finished, out, stream_t, seed, temperature,
+                          sampler[0], sampler[1], eos, capture=capture)
+    for i in range(new - 1):
+        if i and i % EOS_CHECK_EVERY == 0 and bool(finished.all()):
+            break
+        dec.replay()
+    if stats is not None:
+        stats["steps"], stats["new_tokens"] = nsteps.tolist(), ctr.tolist()
+    return new
 
 
 class _null:

@@ -496,7 +496,7 @@ class Trainer:
         return decoded
 
     def generate_responses(self, prompts, max_new_tokens: int, batch_size: int, temperature: float = 0.0,
-                           top_k=None, top_p=None, seed=None, kv_dtype=None, weight_dtype=None):
+                           top_k=None, top_p=None, seed=None, kv_dtype=None, weight_dtype=None, speculative=None):
         """Continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in input
         order, each cut before its first eos: greedy by default; with ``seed`` sampled on the
         device (``temperature``, ``top_k``, ``top_p``: :func:`generate_ragged`), prompt i drawing
@@ -509,7 +509,10 @@ class Trainer:
         generation.  ``kv_dtype="fp8"``: the quantised KV cache of :func:`generate_ragged`.
         ``weight_dtype="fp8"``: its fp8 decode weights; the packs are built once here, from the
         weights as they are now, shared by every batch and dropped on return (nothing is kept
-        across calls: the weights may change in between)."""
+        across calls: the weights may change in between).  ``speculative=K``: exact speculative
+        decoding with K prompt-lookup drafts per step (:func:`generate_ragged`): the same answers
+        in fewer steps where an answer repeats its prompt or itself; prompt i keeps stream i, and
+        a prompt must leave K more positions free."""
         if weight_dtype not in (None, "fp8"):
             raise ValueError(f"generate_responses: weight_dtype must be None or 'fp8', got {weight_dtype!r}")
         tok, cfg = self.loaderObj.tokenizer, self.config
@@ -521,6 +524,9 @@ class Trainer:
             if t.numel() + max_new_tokens > ctx:
                 raise ValueError(f"prompt {i} has {t.numel()} tokens: with max_new_tokens {max_new_tokens} it does "
                                  f"not fit the context length {ctx}")
+            if speculative and t.numel() + max_new_tokens + int(speculative) > ctx:
+                raise ValueError(f"prompt {i} has {t.numel()} tokens: with max_new_tokens {max_new_tokens} and "
+                                 f"speculative {speculative} it does not fit the context length {ctx}")
         order = sorted(range(len(ids)), key=lambda i: ids[i].numel())
         out = [None] * len(ids)
         weights = None
@@ -536,6 +542,8 @@ class Trainer:
                 sampling["kv_dtype"] = kv_dtype
             if weights is not None:
                 sampling["weight_dtype"] = weights
+            if speculative is not None:
+                sampling["speculative"] = speculative
             res = generate_ragged(self.model, [ids[i] for i in rows], max_new_tokens, ctx, eos_id=cfg["eos_id"],
                                   **sampling)
             for i, r in zip(rows, res):

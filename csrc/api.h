@@ -16,6 +16,8 @@ unsigned int debug_take_attn_decode_split();
 unsigned int debug_take_attn_decode_fp8();
 unsigned int debug_take_elementwise();
 unsigned int debug_take_sample();
+unsigned int debug_take_attn_extend();
+unsigned int debug_take_spec();
 
 // norms.hip
 int norm_bwd_num_wg(int N, int d);
@@ -163,6 +165,17 @@ void attn_decode_append_split(DType dt, const void* qkv, void* kc, void* vc, voi
 void attn_decode_split_combine_rows(DType dt, const float* ws, void* out, const int* pos, int B, int H, int hd,
                                     int Tmax, hipStream_t s);
 
+// attn_extend.hip -- Q new tokens per row (2 <= Q <= 8, Q * H/G <= 32; bf16 / fp16, hd 64 / 128):
+// qkv [B Q, (H+2G) hd], row b Q + j = token j of row b at position pos[b] + j (pos int32 [B],
+// pos[b] + Q <= Tmax); appends the Q k / v rows and attends query j over keys 0 .. pos[b] + j.
+// Split-KV partial pass + the combine above over B Q rows; pos_rows int32 [B Q] = pos[b] + j,
+// ws of attn_extend_workspace floats.
+bool attn_extend_supported(int Q, int H, int G);
+bool attn_extend_grid_ok(int B, int G);
+long attn_extend_workspace(int B, int Q, int H, int hd, int Tmax);
+void attn_extend_rows(DType dt, const void* qkv, void* kc, void* vc, void* out, float* ws, const int* pos,
+                      const int* pos_rows, int B, int Q, int H, int G, int hd, int Tmax, hipStream_t s);
+
 // attn_decode_fp8.hip -- the KV cache as e4m3fn bytes k8 / v8 [B, G, Tmax, hd] with one fp32 scale per
 // (row, kv head, position) ks / vs [B, G, Tmax]; dt is the dtype of qkv and out (bf16 / fp16), hd 64 / 128.
 // fill: kv_cache_fill_varlen, quantising.  decode: per-row append + attention in split-KV form for
@@ -195,6 +208,14 @@ void embedding_bwd_pos(DType dt, const void* dx, void* grad, int B, int T, int d
 void sample_rows(DType dt, const void* logits, const int64_t* stream, int* ctr, uint64_t seed, float temperature,
                  int top_k, double top_p, long eos_id, int64_t* next_idx, int64_t* out, long out_ld, int out_cols,
                  unsigned char* finished, float* thr, int64_t* tokens, int B, int V, hipStream_t s);
+
+// spec.hip -- speculative decoding bookkeeping (ops/reference.py:spec_advance is the contract):
+// accept the verified drafts of every live row (accept), then draft the next step's Q input tokens
+// by prompt lookup in hist [B, Lh].  One workgroup per row; Q in 1..8, ngram in 1..4.
+bool spec_advance_supported(int Q, int ngram);
+void spec_advance(int64_t* idx, const int64_t* samp, int* hist, const int* h0, int* pos, int* ctr, int* nsteps,
+                  unsigned char* finished, int64_t* out, long out_stride, int B, int Q, int Lh, int newn,
+                  long eos_id, int ngram, bool accept, hipStream_t s);
 
 // lora.hip — see the file header for the operand conventions
 constexpr int LORA_MAX = 8;

@@ -837,6 +837,38 @@ Tensor attn_decode_append_rows_fp8(const Tensor& qkv, Tensor& k8, Tensor& ks, Te
   return out;
 }
 
+// Q tokens per row over the cache (csrc/attn_extend.hip): qkv [B Q, (H+2G) hd], row b Q + j = token j
+// of row b at position pos[b] + j (pos int32 [B], the caller keeps every pos[b] + Q <= Tmax);
+// pos_rows int32 [B Q] = pos[b] + j (what the merge launch reads) -> out [B Q, H hd]
+Tensor attn_extend_rows(const Tensor& qkv, Tensor& kc, Tensor& vc, const Tensor& pos, const Tensor& pos_rows,
+                        int64_t Q, int64_t H, int64_t G) {
+  Op op("attn_extend_rows", qkv, "qkv");
+  op.dims(qkv, 2, "qkv");
+  op.dims(kc, 4, "kcache");
+  const int64_t B = kc.size(0), hd = kc.size(3), Tmax = kc.size(2);
+  decode_caches(op, qkv, kc, vc, B, H, hd);
+  TORCH_CHECK(G > 0 && bllm::attn_extend_supported(op.to_int(Q, "Q"), op.to_int(H, "H"), op.to_int(G, "G")),
+              "attn_extend_rows: Q must be in 2..8 with Q * (H / G) <= 32, got Q ", Q, " H ", H, " G ", G);
+  TORCH_CHECK(kc.size(1) == G && qkv.size(0) == B * Q && qkv.size(1) == (H + 2 * G) * hd, "attn_extend_rows: qkv ",
+              qkv.sizes(), " / cache ", kc.sizes(), " mismatch for Q ", Q, " H ", H, " G ", G);
+  TORCH_CHECK(Tmax >= Q, "attn_extend_rows: the cache holds ", Tmax, " positions, fewer than Q = ", Q);
+  TORCH_CHECK(aligned(qkv, 16) && aligned(kc, 16) && aligned(vc, 16),
+              "attn_extend_rows: qkv and the caches must be 16-byte aligned");
+  op.vec(pos, B, at::kInt, "pos");
+  op.vec(pos_rows, B * Q, at::kInt, "pos_rows");
+  op.to_int(Tmax, "Tmax");
+  op.to_int(B * Q * H, "B * Q * H");
+  TORCH_CHECK(bllm::attn_extend_grid_ok(op.to_int(B, "B"), (int)G), "attn_extend_rows: B ", B, " or the cache's G ", G,
+              " exceeds the launch grid");
+  auto ws = at::empty({bllm::attn_extend_workspace((int)B, (int)Q, (int)H, (int)hd, (int)Tmax)},
+                      qkv.options().dtype(at::kFloat));
+  auto out = at::empty({B * Q, H * hd}, qkv.options());
+  bllm::attn_extend_rows(dt_of(qkv), qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                         ws.data_ptr<float>(), pos.data_ptr<int>(), pos_rows.data_ptr<int>(), (int)B, (int)Q, (int)H,
+                         (int)G, (int)hd, (int)Tmax, stream());
+  return out;
+}
+
 // qkv [B T, (H + 2G) hd] contiguous; B, T, H, G, hd positive, H a multiple of G -> them as ints
 struct AttnDims { int B, T, H, G, hd; };
 AttnDims attn_args(const Op& op, const Tensor& qkv, int64_t B, int64_t T, int64_t H, int64_t G, int64_t hd) {
@@ -1468,13 +1500,50 @@ Tensor sample_rows(const Tensor& logits, const Tensor& streams, Tensor& ctr, int
   return tokens;
 }
 
+// Speculative decoding bookkeeping (csrc/spec.hip, ops/reference.py:spec_advance): idx / samp int64
+// [B, Q]; hist int32 [B, Lh]; h0 / pos / ctr / nsteps int32 [B]; finished bool [B]; out int64 [B, new]
+void spec_advance_(Tensor& idx, const Tensor& samp, Tensor& hist, const Tensor& h0, Tensor& pos, Tensor& ctr,
+                   Tensor& nsteps, Tensor& finished, Tensor& out, int64_t eos_id, int64_t ngram, bool accept) {
+  Op op("spec_advance_", idx, "idx");
+  op.dims(idx, 2, "idx");
+  const int64_t B = idx.size(0), Q = idx.size(1);
+  TORCH_CHECK(B > 0 && bllm::spec_advance_supported((int)std::min<int64_t>(Q, INT_MAX),
+                                                    (int)std::clamp<int64_t>(ngram, -1, INT_MAX)),
+              "spec_advance_: idx must be [B >= 1, Q in 1..8] and ngram in 1..4, got ", idx.sizes(), " ngram ", ngram);
+  op.shaped(idx, {B, Q}, at::kLong, "idx");
+  op.contig(idx, "idx");
+  op.shaped(samp, {B, Q}, at::kLong, "samp");
+  op.contig(samp, "samp");
+  op.dims(hist, 2, "hist");
+  op.shaped(hist, {B, -1}, at::kInt, "hist");
+  op.contig(hist, "hist");
+  TORCH_CHECK(hist.size(1) >= 1, "spec_advance_: hist has no columns");
+  op.vec(h0, B, at::kInt, "h0");
+  op.vec(pos, B, at::kInt, "pos");
+  op.vec(ctr, B, at::kInt, "ctr");
+  op.vec(nsteps, B, at::kInt, "nsteps");
+  op.vec(finished, B, at::kBool, "finished");
+  op.on_gpu(out, "out");
+  op.dtype(out, at::kLong, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) >= 1 && out.stride(1) == 1 &&
+                  (B == 1 || out.stride(0) >= out.size(1)),
+              "spec_advance_: out must be [", B, ", >= 1] with unit column stride and rows that do not overlap, got ",
+              out.sizes(), " strides ", out.strides());
+  bllm::spec_advance(idx.data_ptr<int64_t>(), samp.data_ptr<int64_t>(), hist.data_ptr<int>(), h0.data_ptr<int>(),
+                     pos.data_ptr<int>(), ctr.data_ptr<int>(), nsteps.data_ptr<int>(),
+                     reinterpret_cast<unsigned char*>(finished.data_ptr<bool>()), out.data_ptr<int64_t>(),
+                     (long)out.stride(0), op.to_int(B, "B"), (int)Q, op.to_int(hist.size(1), "hist columns"),
+                     op.to_int(out.size(1), "out columns"), (long)eos_id, (int)ngram, accept, stream());
+}
+
 // ------------------------------------------------------------------ kernel debug mode
 // First failed device-side check since the last call (common.h DebugCode; 0 = none), over every
 // instrumented translation unit; always 0 in release builds (the checks are compiled away).
 int64_t debug_error() {
   const unsigned codes[] = {bllm::debug_take_embedding(), bllm::debug_take_loss(), bllm::debug_take_attn_decode(),
                             bllm::debug_take_attn_decode_split(), bllm::debug_take_attn_decode_fp8(),
-                            bllm::debug_take_elementwise(), bllm::debug_take_sample()};
+                            bllm::debug_take_elementwise(), bllm::debug_take_sample(),
+                            bllm::debug_take_attn_extend(), bllm::debug_take_spec()};
   for (unsigned c : codes)
     if (c) return (int64_t)c;
   return 0;
@@ -1533,6 +1602,8 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("attn_decode_append_rows(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_rows);
   BLLM_OP("attn_decode_split(Tensor q, Tensor kcache, Tensor vcache, int L) -> Tensor", attn_decode_split);
   BLLM_OP("attn_decode_append_split(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_split);
+  BLLM_OP("attn_extend_rows(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, Tensor pos_rows, int Q, int H, int G) -> Tensor", attn_extend_rows);
+  BLLM_OP("spec_advance_(Tensor(a!) idx, Tensor samp, Tensor(b!) hist, Tensor h0, Tensor(c!) pos, Tensor(d!) ctr, Tensor(e!) nsteps, Tensor(f!) finished, Tensor(g!) out, int eos_id, int ngram, bool accept) -> ()", spec_advance_);
   BLLM_OP("kv_cache_fill_varlen(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) vcache) -> ()", kv_cache_fill_varlen);
   BLLM_OP("kv_cache_fill_varlen_fp8(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale) -> ()", kv_cache_fill_varlen_fp8);
   BLLM_OP("attn_decode_append_rows_fp8(Tensor qkv, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale, Tensor pos, int H, int G) -> Tensor", attn_decode_append_rows_fp8);

@@ -310,6 +310,7 @@ enum DebugCode : unsigned int {
   DBG_DECODE_POS = 3,    // decode: cache position outside [0, Tmax) or beyond the LDS score buffer
   DBG_ROPE_POS = 4,      // rope: device position negative
   DBG_SAMPLE_CTR = 5,    // sampler: row counter outside [0, out.size(1))
+  DBG_SPEC_STATE = 6,    // speculative step: row counter, position or corpus length out of range
 };
 #ifdef BLLM_KERNEL_DEBUG
 #define BLLM_DEBUG_WORD(tu)                                                                        \

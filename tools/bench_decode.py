@@ -38,7 +38,18 @@ Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --context 3
 
 ``--ragged B,... --weight_dtype fp8`` (``--lora_rank R``: on a LoRA model): the decode steps on fp8
 weight packs (``ops.linear_w8``) against the model's own weights, interleaved (``ragged_weights``).
-Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128 --weight_dtype fp8"""
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128 --weight_dtype fp8
+
+``--ragged B,... --speculative K1,K2,... [--hints self]``: exact speculative decoding
+(``generate_ragged(speculative=K)``) against the plain loop, both greedy through the device sampler
+(``seed=0``), interleaved (``ragged_speculative``).  Without hints a random-init model accepts next to
+no draft: the overhead of a verify step.  ``--hints self`` adds arms whose hint is each prompt
+followed by its own answer: nearly every draft accepted, the ceiling.  The answer is the one the
+unhinted arm of the same K gave (``--hints plain``: the plain loop's; in bf16 a random-init model's
+near-tied logits round differently in a 1-token and a (K + 1)-token step, the two answers part after
+some tokens and the hint stops matching there).  Per arm: ms per generated token, verify steps
+per row, accepted drafts per step and whether the tokens equal the plain loop's.
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128 --speculative 3,7 --hints self"""
 import argparse
 import json
 import os
@@ -193,6 +204,54 @@ def ragged_weights(a, m, cfg):
             json.dump(rows, f, indent=1)
 
 
+def ragged_speculative(a, m, cfg):
+    sizes = [int(b) for b in a.ragged.split(",")]
+    ks = [int(k) for k in a.speculative.split(",")]
+    prompts, tok_name = _alpaca_prompts(a.model, cfg, max(sizes))
+    ctx = cfg.context_length
+    rows = []
+    for B in sizes:
+        ps = prompts[:B]
+        plain = [r.cpu() for r in G.generate_ragged(m, ps, a.tokens, ctx, seed=0)]     # also the warm-up
+        arms = {"plain": (None, None)}
+        for k in ks:
+            arms[f"spec{k}"] = (k, None)
+            if a.hints == "plain":
+                arms[f"spec{k}_hinted"] = (k, plain)
+            elif a.hints == "self":
+                arms[f"spec{k}_hinted"] = (k, [r.cpu() for r in G.generate_ragged(m, ps, a.tokens, ctx, seed=0,
+                                                                                   speculative=k)])
+        stats = {k: {} for k in arms}
+
+        def run(arm):
+            k, hints = arms[arm]
+            return G.generate_ragged(m, ps, a.tokens, ctx, seed=0, speculative=k, draft_hints=hints,
+                                     stats=stats[arm] if k else None)
+
+        same = {arm: all(torch.equal(x.cpu(), y) for x, y in zip(run(arm), plain)) for arm in arms}
+        times = {k: [] for k in arms}
+        for _ in range(a.repeats):
+            for k in arms:
+                times[k].append(_timed(lambda: run(k)))
+        row = {"model": f"{a.model}-{a.num_params}", "batch": B, "new_tokens": a.tokens, "repeats": a.repeats,
+               "tokenizer": tok_name, "graph": os.environ.get("BLLM_DECODE_GRAPH", "default")}
+        for k in arms:
+            st = _stats(times[k], B, a.tokens)
+            row[k] = {"ms_per_token": st["ms_per_token"], "ms_per_token_range": st["ms_per_token_range"],
+                      "same_tokens_as_plain": same[k]}
+            if arms[k][0]:
+                steps, drawn = stats[k]["steps"], stats[k]["new_tokens"]
+                row[k]["steps_per_row"] = round(sum(steps) / B, 2)
+                row[k]["accepted_drafts_per_step"] = round(sum(d - 1 - s for d, s in zip(drawn, steps)) /
+                                                           max(sum(steps), 1), 3)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def context_bench(a, m, cfg):
     ctx = cfg.context_length
     if a.prompt + a.tokens > ctx:
@@ -301,6 +360,11 @@ def main():
                     help="--ragged: fp8 compares the decode steps on fp8 weight packs with the model's weights")
     ap.add_argument("--lora_rank", type=int, default=0,
                     help="--weight_dtype fp8: a LoRA model (this rank on every linear, nonzero B), folded into the packs")
+    ap.add_argument("--speculative", default=None,
+                    help="--ragged: comma list of K, speculative decoding against the plain loop (see above)")
+    ap.add_argument("--hints", default="none", choices=["none", "self", "plain"],
+                    help="--speculative: adds arms hinted with each prompt and its own answer (self: the unhinted "
+                         "speculative arm's, plain: the plain loop's)")
     a = ap.parse_args()
     ops.load_ext(required=True)
     cfg = (get_config(a.model, a.num_params) if a.context is None
@@ -319,6 +383,8 @@ def main():
     m.flatten()
     if a.graph is not None:
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
+    if a.ragged and a.speculative:
+        return ragged_speculative(a, m, cfg)
     if a.ragged and a.weight_dtype == "fp8":
         return ragged_weights(a, m, cfg)
     if a.ragged:

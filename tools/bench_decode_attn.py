@@ -17,8 +17,14 @@ on the same values, quantised per row by the oracle; the fp8 arm's rate counts t
 to read, hd + 4 per row (bytes and one fp32 scale), and ``fp8_no_slower`` says whether its median
 time is inside or below the range of the bf16 arm's repeats.
 
+``--extend Q1,Q2,...``: the arms are one token per row (``ops.attn_decode_append_rows``: the
+single-launch kernel up to 8,192 positions, split-KV beyond) and ``ops.attn_extend_rows`` with Q tokens
+per row (csrc/attn_extend.hip), the Q tokens in the cache's last Q positions.  Per Q: the ratio to the
+one-token call and ``cheaper_than_q_calls`` (ratio < Q, what the Q-token step is for); the rates count
+the valid K + V bytes once.
+
 Usage: python tools/bench_decode_attn.py [--shapes llama3_2-1B,llama3-8B,gpt2-774M] [--batch 1,32]
-           [--lengths 1024,8192,32768,131072] [--repeats 5] [--kv model|fp8] [--out FILE]"""
+           [--lengths 1024,8192,32768,131072] [--repeats 5] [--kv model|fp8] [--extend 2,4,8] [--out FILE]"""
 import argparse
 import json
 import os
@@ -113,6 +119,52 @@ def case_fp8(name, B, L, a):
     return row
 
 
+def case_extend(name, B, L, a):
+    H, G, hd = SHAPES[name]
+    dt = torch.bfloat16
+    qs = [int(q) for q in a.extend.split(",")]
+    nbytes = kv_bytes(B, G, L, hd)
+    nbuf = max(1, min(16, (1 << 30) // nbytes + 1))
+    caches = [(torch.empty(B, G, L, hd, device="cuda", dtype=dt).normal_(),
+               torch.empty(B, G, L, hd, device="cuda", dtype=dt).normal_()) for _ in range(nbuf)]
+    qkv = {q: torch.randn(B * q, (H + 2 * G) * hd, device="cuda").to(dt) for q in [1] + qs}
+    pos = {q: torch.full((B,), L - q, dtype=torch.int32, device="cuda") for q in [1] + qs}
+    pos_rows = {q: (pos[q][:, None] + torch.arange(q, dtype=torch.int32, device="cuda")).reshape(-1) for q in qs}
+
+    def one(i):
+        kc, vc = caches[i % nbuf]
+        return ops.attn_decode_append_rows(qkv[1], kc, vc, pos[1], H, G)
+
+    def extend(q):
+        def fn(i):
+            kc, vc = caches[i % nbuf]
+            return ops.attn_extend_rows(qkv[q], kc, vc, pos[q], q, H, G, pos_rows=pos_rows[q])
+        return fn
+
+    arms = {"one": one}
+    for q in qs:
+        arms[f"extend{q}"] = extend(q)
+    times = {k: [] for k in arms}
+    iters = {}
+    for k, fn in arms.items():
+        _window(fn, 3)
+        iters[k] = max(3, min(2000, int(a.window_ms * 1000.0 / max(_window(fn, 5), 1.0))))
+    for _ in range(a.repeats):
+        for k, fn in arms.items():
+            times[k].append(_window(fn, iters[k]))
+    row = {"shape": name, "H": H, "G": G, "hd": hd, "B": B, "L": L, "kv_bytes": nbytes, "caches": nbuf,
+           "repeats": a.repeats}
+    for k in arms:
+        row[k] = _stats(times[k], nbytes)
+        row[k]["iters"] = iters[k]
+    for q in qs:
+        r = row[f"extend{q}"]
+        r["ratio_to_one"] = round(r["us"] / row["one"]["us"], 3)
+        r["cheaper_than_q_calls"] = r["us"] < q * row["one"]["us"]
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def case(name, B, L, a):
     H, G, hd = SHAPES[name]
     dt = torch.bfloat16
@@ -165,6 +217,8 @@ def main():
     ap.add_argument("--window_ms", type=float, default=40.0)
     ap.add_argument("--kv", default="model", choices=["model", "fp8"],
                     help="fp8: the bf16 split-KV kernel against the fp8-cache kernel")
+    ap.add_argument("--extend", default=None,
+                    help="comma list of Q: one token per row against attn_extend_rows with Q tokens per row")
     ap.add_argument("--out", default=None, help="also write the rows to this JSON file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -175,7 +229,8 @@ def main():
     for name in a.shapes.split(","):
         for B in (int(b) for b in a.batch.split(",")):
             for L in (int(x) for x in a.lengths.split(",")):
-                rows.append((case_fp8 if a.kv == "fp8" else case)(name, B, L, a))
+                fn = case_extend if a.extend else (case_fp8 if a.kv == "fp8" else case)
+                rows.append(fn(name, B, L, a))
                 torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
