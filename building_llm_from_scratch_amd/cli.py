@@ -49,15 +49,15 @@ def perform_checks(args):
         raise ValueError("--generate_seed must fit 64 bits.")
     if getattr(args, "generate_kv_dtype", "model") not in ("model", "fp8"):
         raise ValueError("--generate_kv_dtype must be 'model' or 'fp8'.")
-    if getattr(args, "generate_weight_dtype", "model") not in ("model", "fp8"):
-        raise ValueError("--generate_weight_dtype must be 'model' or 'fp8'.")
+    if getattr(args, "generate_weight_dtype", "model") not in ("model", "fp8", "mxfp4"):
+        raise ValueError("--generate_weight_dtype must be 'model', 'fp8' or 'mxfp4'.")
     spec = getattr(args, "generate_speculative", 0)
     if not 0 <= spec <= 7:
         raise ValueError("--generate_speculative must be in 0..7 (0: off).")
     if spec and (getattr(args, "generate_kv_dtype", "model") == "fp8"
-                 or getattr(args, "generate_weight_dtype", "model") == "fp8"):
+                 or getattr(args, "generate_weight_dtype", "model") != "model"):
         raise ValueError("--generate_speculative runs on the default cache and weights: not with "
-                         "--generate_kv_dtype fp8 or --generate_weight_dtype fp8.")
+                         "--generate_kv_dtype fp8 or --generate_weight_dtype fp8 / mxfp4.")
     if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -194,7 +194,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="weights of the decode steps of --generate_prompts: 'model' uses the model's own; 'fp8' runs "
                         "every projection on e4m3 packs with one fp32 scale per output channel, LoRA folded in, built "
                         "once per run of the prompts (extra memory, about half the 16-bit weights; the first token "
-                        "of an answer still comes from the exact weights; answers can differ)")
+                        "of an answer still comes from the exact weights; answers can differ); 'mxfp4' packs the "
+                        "projections whose input width is a multiple of 128 as e2m1 codes with one power-of-two scale "
+                        "per 32 inputs instead (0.53 of the fp8 bytes, a larger quantisation error; the head and the "
+                        "other projections stay fp8)")
     x.add_argument("--generate_speculative", type=int, default=0,
                    help="exact speculative decoding of --generate_prompts: K drafts per step (1..7) by prompt lookup, "
                         "the continuation of the latest earlier occurrence of the answer's last two tokens in its own "
@@ -287,8 +290,8 @@ def _generate_responses(trainer, args, rank, out_dir):
                         seed=args.generate_seed)
     if getattr(args, "generate_kv_dtype", "model") == "fp8":
         sampling["kv_dtype"] = "fp8"
-    if getattr(args, "generate_weight_dtype", "model") == "fp8":
-        sampling["weight_dtype"] = "fp8"
+    if getattr(args, "generate_weight_dtype", "model") in ("fp8", "mxfp4"):
+        sampling["weight_dtype"] = args.generate_weight_dtype
     if getattr(args, "generate_speculative", 0):
         sampling["speculative"] = args.generate_speculative
     responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size, **sampling)

@@ -676,13 +676,19 @@ class BaseLM(nn.Module):
 
         A snapshot of the weights as they are now, and extra memory on top of them (about half
         the bytes of 16-bit weights): a speed feature, not a capacity one.  Call inside
-        ``engine.params_resident()`` (a sharding FSDP engine then hands it whole weights)."""
-        if weight_dtype != "fp8":
-            raise ValueError(f"new_decode_weights: weight_dtype must be 'fp8', got {weight_dtype!r}")
+        ``engine.params_resident()`` (a sharding FSDP engine then hands it whole weights).
+
+        ``weight_dtype="mxfp4"``: the groups are :class:`LinearW4` instead (``ops.w4_pack``: e2m1
+        codes with one power-of-two scale per 32 consecutive k, 0.53 of the fp8 bytes and a larger
+        quantisation error), with two exceptions: the head stays an fp8 pack (its logits decide the
+        token), and a group whose K is no multiple of ``ops.W4_K_GRANULE`` keeps its fp8 pack
+        (``FusedLinear.decode_pack``), so that no projection of a step leaves the kernels."""
+        if weight_dtype not in ("fp8", "mxfp4"):
+            raise ValueError(f"new_decode_weights: weight_dtype must be 'fp8' or 'mxfp4', got {weight_dtype!r}")
         self._ensure_flat()
         self._rctx.sync_all_params()
         comps = self._comps
-        return DecodeWeights([tuple(fl.w8_pack() for fl in c.w8_groups()) for c in comps[1:-1]],
+        return DecodeWeights([tuple(fl.decode_pack(weight_dtype) for fl in c.w8_groups()) for c in comps[1:-1]],
                              comps[-1].head.w8_pack())
 
     @torch.no_grad()

@@ -181,9 +181,9 @@ class GPTBlockCompute(UnitCompute):
         """Everything after attention (inference: no dropout): out projection, residual, GELU MLP."""
         b = self.block
         if weights is not None:
-            x2 = x2d + self.o.forward_w8(o, weights[1])
-            f = self.fc.forward_w8(self._ln(x2, b.norm2)[0], weights[2])
-            return x2 + self.proj.forward_w8(ops.gelu_fwd(f), weights[3])
+            x2 = x2d + self.o.forward_pack(o, weights[1])
+            f = self.fc.forward_pack(self._ln(x2, b.norm2)[0], weights[2])
+            return x2 + self.proj.forward_pack(ops.gelu_fwd(f), weights[3])
         a, _ = self.o.forward(o)
         x2 = x2d + a
         f, _ = self.fc.forward(self._ln(x2, b.norm2)[0])
@@ -192,13 +192,13 @@ class GPTBlockCompute(UnitCompute):
 
     def infer_rows(self, x2d, pos_rows, kv, weights=None, q_per_row: int = 1, pos_b=None):
         """``infer_dev`` with a position per row (int32 [B] on the device).  ``weights``: the
-        block's fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``.
+        block's packs (``new_decode_weights``, fp8 or MXFP4); its four projections then run ``forward_pack``.
         ``q_per_row=Q > 1``: Q consecutive tokens per batch row (rows b*Q + j, ``pos_b`` int32 [B]
         = the batch rows' positions ``pos_rows[::Q]``); attention is ``ops.attn_extend_rows``."""
         H = self.rctx.cfg.n_heads
         h1 = self._ln(x2d, self.block.norm1)[0]
         if weights is not None:
-            qkv = self.qkv.forward_w8(h1, weights[0])
+            qkv = self.qkv.forward_pack(h1, weights[0])
         else:
             qkv, _ = self.qkv.forward(h1)
         if q_per_row != 1:

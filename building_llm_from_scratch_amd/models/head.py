@@ -53,11 +53,11 @@ class HeadComputeMixin:
         self.head.bind(unit)
 
     def infer(self, x2d, B, t, weights=None):
-        """Logits of each row's last position.  ``weights``: the head's fp8 pack
-        (``new_decode_weights``: vocabulary rows, one scale each); the projection is ``forward_w8``."""
+        """Logits of each row's last position.  ``weights``: the head's decode pack
+        (``new_decode_weights``: vocabulary rows, fp8 for both weight dtypes); the projection is ``forward_pack``."""
         last = x2d.view(B, t, -1)[:, -1, :].contiguous()
         if weights is not None:
-            return self.head.forward_w8(self._norm_fwd(last)[0], weights)
+            return self.head.forward_pack(self._norm_fwd(last)[0], weights)
         logits, _ = self.forward_logits(last, save=False)
         return logits
 

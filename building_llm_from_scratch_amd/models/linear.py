@@ -228,6 +228,8 @@ LowRankDx = namedtuple("LowRankDx", "base u P scale")
 # a projection group for the decode step on fp8 weights: the ops.W8Pack of its effective weight
 # (LoRA folded in) and its bias or None (FusedLinear.w8_pack / forward_w8)
 LinearW8 = namedtuple("LinearW8", "pack bias")
+# the same on MXFP4 weights: the ops.W4Pack and the bias or None (FusedLinear.w4_pack / forward_w4)
+LinearW4 = namedtuple("LinearW4", "pack bias")
 
 
 class FrozenDerived:
@@ -434,6 +436,40 @@ class FusedLinear:
         if residual is not None:
             assert pack.bias is None
         return ops.linear_w8(x, pack.pack, pack.bias, residual)
+
+    # ------------------------------------------------------------------ MXFP4 decode weights
+    def w4_pack(self) -> "LinearW4":
+        """The group's decode-only MXFP4 pack (``ops.w4_pack``: e2m1 codes, one E8M0 scale per 32
+        consecutive k) of the same effective weight as ``w8_pack`` -- LoRA folded in fp32, then
+        quantised -- and a copy of its bias.  A snapshot, and a coarser one than fp8."""
+        W = self.W().detach().to(torch.float32, copy=self.has_lora)
+        for (c0, c1), s in zip(self.cols, self.specs):
+            if s.lora_A is not None:
+                A, B = self.unit.data(s.lora_A).float(), self.unit.data(s.lora_B).float()
+                W[c0:c1] += s.scaling * (A @ B).t()
+        b = self.b()
+        return LinearW4(ops.w4_pack(W), None if b is None else b.detach().clone())
+
+    def forward_w4(self, x: torch.Tensor, pack: "LinearW4", residual: Optional[torch.Tensor] = None):
+        """``forward`` on the group's MXFP4 pack: one ``ops.linear_w4`` call -> y."""
+        if residual is not None:
+            assert pack.bias is None
+        return ops.linear_w4(x, pack.pack, pack.bias, residual)
+
+    def decode_pack(self, weight_dtype: str):
+        """The group's pack for ``new_decode_weights(weight_dtype)``: ``"mxfp4"`` gives a
+        :class:`LinearW4` where the kernel takes the group's K (a multiple of
+        ``ops.W4_K_GRANULE``) and the fp8 pack otherwise, so that no group of a decode step falls
+        to the fp64 oracle; ``"fp8"`` gives ``w8_pack()``."""
+        if weight_dtype == "mxfp4" and self.W().shape[1] % ops.W4_K_GRANULE == 0:
+            return self.w4_pack()
+        return self.w8_pack()
+
+    def forward_pack(self, x: torch.Tensor, pack, residual: Optional[torch.Tensor] = None):
+        """``forward_w4`` or ``forward_w8``, by the pack's type."""
+        if isinstance(pack, LinearW4):
+            return self.forward_w4(x, pack, residual)
+        return self.forward_w8(x, pack, residual)
 
     def forward_swiglu(self, x: torch.Tensor):
         """Gate/up projection with the SwiGLU forward in the GEMM epilogue (``[fc1; fc2]``, no

@@ -275,17 +275,17 @@ class LlamaBlockCompute(UnitCompute):
         u, b = self.unit, self.block
         h1, _ = ops.rmsnorm_fwd(x2d, u.data(b.norm1.weight), self.rctx.cfg.norm_eps)
         if weights is not None:
-            return self.qkv.forward_w8(h1, weights[0])
+            return self.qkv.forward_pack(h1, weights[0])
         return self.qkv.forward(h1)[0]
 
     def _infer_out(self, x2d, o, weights=None):
         """Everything after attention: out projection + residual, norm2, SwiGLU MLP + residual."""
         u, b = self.unit, self.block
         if weights is not None:
-            x2 = self.o.forward_w8(o, weights[1], residual=x2d)
+            x2 = self.o.forward_pack(o, weights[1], residual=x2d)
             h2, _ = ops.rmsnorm_fwd(x2, u.data(b.norm2.weight), self.rctx.cfg.norm_eps)
-            gu = self.gu.forward_w8(h2, weights[2])
-            return self.down.forward_w8(ops.swiglu_fwd(gu), weights[3], residual=x2)
+            gu = self.gu.forward_pack(h2, weights[2])
+            return self.down.forward_pack(ops.swiglu_fwd(gu), weights[3], residual=x2)
         x2, _ = self.o.forward(o, residual=x2d)
         h2, _ = ops.rmsnorm_fwd(x2, u.data(b.norm2.weight), self.rctx.cfg.norm_eps)
         gu, _ = self.gu.forward(h2)
@@ -295,7 +295,7 @@ class LlamaBlockCompute(UnitCompute):
     def infer_rows(self, x2d, pos_rows, kv, weights=None, q_per_row: int = 1, pos_b=None):
         """``infer_dev`` with a position per row (int32 [B] on the device): RoPE rotates row b at
         ``pos_rows[b]`` and the decode kernel appends and attends there.  ``weights``: the block's
-        fp8 packs (``new_decode_weights``); its four projections then run ``forward_w8``.
+        packs (``new_decode_weights``, fp8 or MXFP4); its four projections then run ``forward_pack``.
         ``q_per_row=Q > 1``: Q consecutive tokens per batch row (rows b*Q + j, ``pos_b`` int32 [B]
         = the batch rows' positions ``pos_rows[::Q]``); attention is ``ops.attn_extend_rows``."""
         cfg = self.rctx.cfg

@@ -32,6 +32,7 @@ __all__ = [
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
     "gemm_nn_", "gemm_nt_", "gemm_nn_ok", "dgrad_gemm_enabled", "transpose2d", "dgrad_wt_enabled", "attn_keep_mask",
     "W8Pack", "w8_pack", "w8_unpack", "linear_w8",
+    "W4Pack", "w4_pack", "w4_unpack", "linear_w4",
 ]
 
 rope_tables = ref.rope_tables
@@ -646,6 +647,77 @@ def linear_w8(x: torch.Tensor, pack: W8Pack, bias: Optional[torch.Tensor] = None
         return _k().linear_w8(x, pack.data, pack.scale, bias, residual)
     q, s = w8_unpack(pack)
     return ref.linear_w8(x, q, s, bias, residual)
+
+
+# --------------------------------------------------------------------------- MXFP4 decode weights
+W4_ROW_TILE = 16     # rows of a pack tile (csrc/linear_w4.hip W4_TN: one v_mfma_f32_16x16x32 A operand)
+W4_K_GRANULE = 128   # k per 1-KiB block of a tile (W4_KG): 64 lanes x 16 bytes x 2 codes
+W4_WAVES = 8         # waves of a workgroup = contiguous K slices (W4_WAVES)
+W4_BLOCK = ref.MX4_BLOCK   # k per E8M0 scale
+
+
+class W4Pack(NamedTuple):
+    """A weight ``W [N, K]`` in the MXFP4 format of ``mx4_quantize_rows`` over its rows (e2m1 codes
+    ``[N, K/2]``, two to a byte, and E8M0 bytes ``[N, K/32]``; ``mx4_dequantize`` gives the weight).
+
+    ``data`` and ``scale`` (uint8, 1-D) hold them.  ``tiled``: in the order csrc/linear_w4.hip
+    streams them -- N padded to ``W4_ROW_TILE`` with zero codes and scale byte 127, and for tile t
+    and K block kb the KiB ``data[t][kb][g][r][b] = codes[16 t + r][64 kb + 16 g + b]`` (g < 4,
+    r < 16, b < 16: a lane's 16 bytes are one 32-wide MX block) with its 64 scale bytes
+    ``scale[t][kb][g][r] = scales[16 t + r][4 kb + g]``.  Not tiled (K is no multiple of
+    ``W4_K_GRANULE``): both row-major, for the oracle path only."""
+    data: torch.Tensor
+    scale: torch.Tensor
+    N: int
+    K: int
+    tiled: bool
+
+
+def w4_pack(W: torch.Tensor) -> W4Pack:
+    """Quantise and lay out a weight [N, K] (any float dtype, any device, K a multiple of 32) for
+    ``linear_w4``.  Torch ops only (it runs once per generation call, not per step); the same values
+    give the same bytes on the CPU and on the GPU.  A non-finite weight raises ValueError."""
+    if W.dim() != 2 or W.shape[0] < 1 or W.shape[1] < W4_BLOCK or W.shape[1] % W4_BLOCK:
+        raise ValueError(f"w4_pack: W must be [N, K] with K a positive multiple of {W4_BLOCK}, got {tuple(W.shape)}")
+    N, K = W.shape
+    c, s = ref.mx4_quantize_rows(W)
+    if K % W4_K_GRANULE:
+        return W4Pack(c.reshape(-1).contiguous(), s.reshape(-1).contiguous(), N, K, False)
+    T = -(-N // W4_ROW_TILE)
+    if T * W4_ROW_TILE != N:
+        c = torch.cat([c, c.new_zeros(T * W4_ROW_TILE - N, K // 2)], 0)
+        s = torch.cat([s, s.new_full((T * W4_ROW_TILE - N, K // W4_BLOCK), 127)], 0)
+    nkb = K // W4_K_GRANULE
+    data = c.view(T, W4_ROW_TILE, nkb, 4, 16).permute(0, 2, 3, 1, 4).reshape(-1).contiguous()
+    scale = s.view(T, W4_ROW_TILE, nkb, 4).permute(0, 2, 3, 1).reshape(-1).contiguous()
+    return W4Pack(data, scale, N, K, True)
+
+
+def w4_unpack(pack: W4Pack):
+    """-> (codes [N, K/2] uint8, scale [N, K/32] uint8): the inverse of ``w4_pack``, bit for bit."""
+    N, K = pack.N, pack.K
+    if not pack.tiled:
+        return pack.data.view(N, K // 2), pack.scale.view(N, K // W4_BLOCK)
+    T, nkb = -(-N // W4_ROW_TILE), K // W4_K_GRANULE
+    c = pack.data.view(T, nkb, 4, W4_ROW_TILE, 16).permute(0, 3, 1, 2, 4).reshape(T * W4_ROW_TILE, K // 2)
+    s = pack.scale.view(T, nkb, 4, W4_ROW_TILE).permute(0, 3, 1, 2).reshape(T * W4_ROW_TILE, K // W4_BLOCK)
+    return c[:N].contiguous(), s[:N].contiguous()
+
+
+def linear_w4(x: torch.Tensor, pack: W4Pack, bias: Optional[torch.Tensor] = None,
+              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y[m, n] = round(sum_k x[m, k] w[n, k] + bias[n] + residual[m, n])`` for x [M, K] and an
+    MXFP4 weight pack (w its dequantised weight), fp32 accumulation, y in x's dtype
+    (``ops.reference.linear_w4`` is the contract).  bf16 / fp16 GPU tensors with a tiled pack run
+    the HIP kernel (csrc/linear_w4.hip: one launch, deterministic, a row of y independent of the
+    other rows and of M, graph-capturable); CPU tensors, fp32 and packs of other K run the oracle."""
+    if x.dim() != 2 or x.shape[1] != pack.K:
+        raise ValueError(f"linear_w4: x must be [M, {pack.K}], got {tuple(x.shape)}")
+    if x.device.type == "cuda" and x.dtype in (torch.bfloat16, torch.float16) and pack.tiled and x.shape[0] > 0:
+        load_ext(required=True)
+        return _k().linear_w4(x, pack.data, pack.scale, pack.N, bias, residual)
+    c, s = w4_unpack(pack)
+    return ref.linear_w4(x, c, s, bias, residual)
 
 
 def transpose2d(a: torch.Tensor) -> torch.Tensor:

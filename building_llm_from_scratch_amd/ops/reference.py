@@ -709,6 +709,79 @@ def linear_w8(x, q, s, bias=None, residual=None):
     return v.to(x.dtype)
 
 
+# ------------------------------------------------------------------ MXFP4 decode weights (csrc/linear_w4.hip oracle)
+# The format (OCP MX): a row x (its last dimension, read as fp32) is cut into blocks of 32
+# consecutive elements; a block is 32 e2m1 codes and one E8M0 scale byte.
+#   scale: a = max |x| over the block; e = the smallest integer with a <= 6 * 2^e, found from
+#       a = m * 2^p, m in [0.5, 1) (frexp, no floating-point log2): e = p - 3 if m <= 0.75, else
+#       p - 2; clamped to [-126, 127]; a == 0 gives e = 0.  The byte is e + 127, so byte << 23 is
+#       the fp32 2^e bit for bit, and 255 is never written.  The largest element is never clipped
+#       (the floor(log2 a) - 2 rule saturates a maximum in (6, 8) * 2^e by up to 25 %).
+#   code: sign bit (8) + 3 bits; magnitudes MX4_VALUES[0..7]; x / 2^e (exact) is rounded to the
+#       nearest magnitude, ties to the even code: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2,
+#       2.5 -> 2, 3.5 -> 4, 5 -> 4.  A value that rounds to zero gets code 0 whatever its sign.
+#   storage: two codes to a byte, element 2 i in the low nibble.
+#   dequantised value: magnitude * 2^e, exact in fp32 and bf16 (in fp16 while 2^-13 <= 2^e <= 2^13).
+#   error: |x - dequantised| <= max(|x| / 4, 2^e / 4) per element -- the magnitudes from 1 up are at
+#       most a quarter of the smaller neighbour apart from a midpoint, the ones below 1 are 0.5 apart.
+MX4_BLOCK = 32
+MX4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx4_quantize_rows(x):
+    """x [..., K] (bf16 / fp16 / fp32, K a multiple of 32) -> (codes uint8 [..., K/2], scale uint8
+    [..., K/32]) in the MXFP4 format above.  Torch ops only: the same values give the same bytes on
+    the CPU and on the GPU.  Per element ``|x - mx4_dequantize(...)| <= max(|x| / 4, 2^e / 4)``
+    with e the block's exponent.  A non-finite x raises ValueError."""
+    K = x.shape[-1]
+    if x.dim() < 1 or K < MX4_BLOCK or K % MX4_BLOCK:
+        raise ValueError(f"mx4_quantize_rows: the last dimension must be a positive multiple of {MX4_BLOCK}, "
+                         f"got {tuple(x.shape)}")
+    xf = x.float()
+    if not bool(torch.isfinite(xf).all()):
+        raise ValueError("mx4_quantize_rows: x has non-finite values")
+    xb = xf.reshape(*x.shape[:-1], K // MX4_BLOCK, MX4_BLOCK)
+    a = xb.abs().amax(dim=-1)
+    m, p = torch.frexp(a)
+    e = torch.where(m <= 0.75, p - 3, p - 2).clamp(-126, 127)
+    e = torch.where(a > 0, e, torch.zeros_like(e)).to(torch.int32)
+    two_e = ((e + 127) << 23).view(torch.float32)
+    v = (xb / two_e[..., None]).abs()
+    code = ((v > 0.25).to(torch.uint8) + (v >= 0.75).to(torch.uint8) + (v > 1.25).to(torch.uint8)
+            + (v >= 1.75).to(torch.uint8) + (v > 2.5).to(torch.uint8) + (v >= 3.5).to(torch.uint8)
+            + (v > 5.0).to(torch.uint8))
+    code = code + (((xb < 0) & (code > 0)).to(torch.uint8) << 3)
+    code = code.reshape(*x.shape[:-1], K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), (e + 127).to(torch.uint8)
+
+
+def mx4_dequantize(codes, scale, dtype=torch.float32):
+    """codes uint8 [..., K/2] and scale uint8 [..., K/32] -> [..., K] of ``dtype`` (exact in fp32)."""
+    K = codes.shape[-1] * 2
+    c = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(*codes.shape[:-1], K // MX4_BLOCK, MX4_BLOCK)
+    mag = torch.tensor(MX4_VALUES, dtype=torch.float32, device=codes.device)[(c & 7).long()]
+    mag = torch.where((c & 8) != 0, -mag, mag)
+    two_e = (scale.to(torch.int32) << 23).view(torch.float32)
+    return (mag * two_e[..., None]).reshape(*codes.shape[:-1], K).to(dtype)
+
+
+def linear_w4(x, codes, scale, bias=None, residual=None):
+    """Reference for the MXFP4-weight projection, in fp64: x [M, K], codes [N, K/2] and scale
+    [N, K/32] (``mx4_quantize_rows`` of a weight's rows) ->
+    ``y[m, n] = sum_k x[m, k] w[n, k] + bias[n] + residual[m, n]`` in x's dtype, w the dequantised
+    weight; for fp16 x it is rounded to fp16 first, as the kernel's conversion does (exact while
+    2^-13 <= 2^e <= 2^13)."""
+    w = mx4_dequantize(codes, scale)
+    if x.dtype == torch.float16:
+        w = w.to(torch.float16)
+    v = x.double() @ w.double().t()
+    if bias is not None:
+        v = v + bias.double()
+    if residual is not None:
+        v = v + residual.double()
+    return v.to(x.dtype)
+
+
 # ------------------------------------------------------------------ LoRA (csrc/lora.hip oracle)
 def lora_down(x, ws, c0, lens, ocol, R: int, scale: float = 1.0):
     """out[:, ocol_i : ocol_i + r_i] = scale * x[:, c0_i : c0_i + len_i] @ w_i[:, :len_i]^T"""

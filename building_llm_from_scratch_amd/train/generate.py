@@ -367,6 +367,11 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     quantised weights, so the tokens can differ from the default's.  The packs are extra memory,
     about half the bytes of 16-bit weights.  None: the model's weights, as before.
 
+    ``weight_dtype="mxfp4"`` is the same on MXFP4 packs (``ops.linear_w4``: e2m1 codes, one
+    power-of-two scale per 32 consecutive k, 0.53 of the fp8 bytes) for every projection group
+    whose K is a multiple of 128; the other groups and the head keep their fp8 packs.  Its
+    quantisation error is larger than fp8's, so more tokens can differ from the default's.
+
     ``speculative=K`` (1..7): exact speculative decoding with prompt-lookup drafts.  After the
     first token every step feeds each row its last token and K drafts -- the continuation of the
     latest earlier occurrence of the row's trailing ``SPEC_NGRAM`` tokens in its own text, or in
@@ -386,9 +391,9 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
     from ..models.base import DecodeWeights, pack_prompts
     if kv_dtype not in (None, "fp8"):
         raise ValueError(f"generate_ragged: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
-    if weight_dtype is not None and weight_dtype != "fp8" and not isinstance(weight_dtype, DecodeWeights):
-        raise ValueError("generate_ragged: weight_dtype must be None, 'fp8' or the model's new_decode_weights(), "
-                         f"got {weight_dtype!r}")
+    if weight_dtype is not None and weight_dtype not in ("fp8", "mxfp4") and not isinstance(weight_dtype, DecodeWeights):
+        raise ValueError("generate_ragged: weight_dtype must be None, 'fp8', 'mxfp4' or the model's "
+                         f"new_decode_weights(), got {weight_dtype!r}")
     if not isinstance(prompts, (list, tuple)) or len(prompts) == 0:
         raise ValueError("generate_ragged: prompts must be a non-empty list of 1-D token tensors")
     for b, p in enumerate(prompts):
@@ -432,7 +437,7 @@ def generate_ragged(model, prompts, max_new_tokens: int, context_size: int, temp
         dec = None
         kw = {}
         if weight_dtype is not None:
-            kw["weights"] = model.new_decode_weights("fp8") if weight_dtype == "fp8" else weight_dtype
+            kw["weights"] = model.new_decode_weights(weight_dtype) if isinstance(weight_dtype, str) else weight_dtype
         if sampler is not None:
             stream_t = torch.tensor(sampler[2], dtype=torch.long).to(device)
             ctr = torch.zeros(B, dtype=torch.int32, device=device)    # row b has drawn ctr[b] tokens

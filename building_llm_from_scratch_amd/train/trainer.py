@@ -507,14 +507,14 @@ class Trainer:
         engines gather parameters collectively, as for the sample print).  A prompt longer than
         ``context_length - max_new_tokens`` raises ValueError naming its index, before any
         generation.  ``kv_dtype="fp8"``: the quantised KV cache of :func:`generate_ragged`.
-        ``weight_dtype="fp8"``: its fp8 decode weights; the packs are built once here, from the
+        ``weight_dtype="fp8"`` / ``"mxfp4"``: its fp8 / MXFP4 decode weights; the packs are built once here, from the
         weights as they are now, shared by every batch and dropped on return (nothing is kept
         across calls: the weights may change in between).  ``speculative=K``: exact speculative
         decoding with K prompt-lookup drafts per step (:func:`generate_ragged`): the same answers
         in fewer steps where an answer repeats its prompt or itself; prompt i keeps stream i, and
         a prompt must leave K more positions free."""
-        if weight_dtype not in (None, "fp8"):
-            raise ValueError(f"generate_responses: weight_dtype must be None or 'fp8', got {weight_dtype!r}")
+        if weight_dtype not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"generate_responses: weight_dtype must be None, 'fp8' or 'mxfp4', got {weight_dtype!r}")
         tok, cfg = self.loaderObj.tokenizer, self.config
         ctx = cfg["context_length"]
         ids = [text_to_token_ids(t, tok, cfg)[0] for t in prompts]

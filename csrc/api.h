@@ -325,6 +325,15 @@ bool linear_w8_supported(int M, int N, int K);
 void linear_w8(DType dt, const void* x, const void* wp, const float* scale, const void* bias, const void* res,
                void* y, int M, int N, int K, hipStream_t s);
 
+// linear_w4.hip — the same projection on an MXFP4 pack: wp = the e2m1 codes of W [N, K] in the tile
+// order of ops.w4_pack (N padded to row tiles, K whole granules, half a byte per weight), sp = one
+// E8M0 byte per 32-wide block in the same order (the format of mx4_quantize_rows over the rows of W)
+int linear_w4_row_tile();    // ops.W4_ROW_TILE
+int linear_w4_k_granule();   // ops.W4_K_GRANULE
+bool linear_w4_supported(int M, int N, int K);
+void linear_w4(DType dt, const void* x, const void* wp, const void* sp, const void* bias, const void* res, void* y,
+               int M, int N, int K, hipStream_t s);
+
 // optim.hip
 void adamw_step(DType pdt, DType gdt, void* param, float* master, const void* grad, float* m, float* v, long n,
                 double lr, double b1, double b2, double eps, double wd, int step, const float* gscale,

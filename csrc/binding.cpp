@@ -1458,6 +1458,36 @@ Tensor linear_w8(const Tensor& x, const Tensor& packed, const Tensor& scale, con
   return y;
 }
 
+// ------------------------------------------------------------------ MXFP4-weight projection
+// The same on an MXFP4 pack (csrc/linear_w4.hip): packed = the code bytes of ops.w4_pack (uint8, N
+// padded to row tiles, times K / 2), scale = its E8M0 bytes (uint8, padded N times K / 32); N is
+// passed, since neither length gives it
+Tensor linear_w4(const Tensor& x, const Tensor& packed, const Tensor& scale, int64_t N,
+                 const optional<Tensor>& bias_, const optional<Tensor>& residual_) {
+  Op op("linear_w4", x, "x");
+  op.half_only(x, "x");
+  op.contig(x, "x");
+  op.dims(x, 2, "x");
+  const int64_t M = x.size(0), K = x.size(1), TN = bllm::linear_w4_row_tile();
+  const int m = op.to_int(M, "M"), n = op.to_int(N, "N"), k = op.to_int(K, "K");
+  TORCH_CHECK(bllm::linear_w4_supported(m, n, k) && K <= kMaxGemmPitch, op.name, ": x ", x.sizes(), " with ", N,
+              " output rows: M, N >= 1 and K a positive multiple of ", bllm::linear_w4_k_granule(), ", at most ",
+              kMaxGemmPitch);
+  const int64_t Np = (N + TN - 1) / TN * TN;
+  op.vec(packed, Np * K / 2, at::kByte, "packed");
+  op.vec(scale, Np * K / 32, at::kByte, "scale");
+  const Tensor* bias = opt(bias_);
+  const Tensor* res = opt(residual_);
+  if (bias) op.vec(*bias, N, x.scalar_type(), "bias");
+  if (res) op.shaped(*res, {M, N}, x.scalar_type(), "residual");
+  TORCH_CHECK(aligned(x, 16) && aligned(packed, 16) && (!res || aligned(*res, 16)), op.name,
+              ": x, packed and residual must be 16-byte aligned");
+  auto y = at::empty({M, N}, x.options());
+  bllm::linear_w4(dt_of(x), x.data_ptr(), packed.data_ptr(), scale.data_ptr(), opt_ptr(bias), opt_ptr(res),
+                  y.data_ptr(), m, n, k, stream());
+  return y;
+}
+
 // ------------------------------------------------------------------ sampler
 // logits [B, V] -> tokens int64 [B]: temperature (0: argmax), top-k (0 or >= V: off), top-p (1: off)
 // and a Gumbel-max draw from the counter-based stream (seed, stream[b], ctr[b]) (csrc/sample.hip).
@@ -1578,6 +1608,8 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("transpose2d(Tensor a) -> Tensor", transpose2d);
   BLLM_OP("linear_residual(Tensor x, Tensor W, Tensor C) -> Tensor", linear_residual);
   BLLM_OP("linear_w8(Tensor x, Tensor packed, Tensor scale, Tensor? bias, Tensor? residual) -> Tensor", linear_w8);
+  BLLM_OP("linear_w4(Tensor x, Tensor packed, Tensor scale, int N, Tensor? bias, Tensor? residual) -> Tensor",
+          linear_w4);
   BLLM_OP("swiglu_fwd(Tensor gu) -> Tensor", swiglu_fwd);
   BLLM_OP("swiglu_fwd_into_(Tensor gu, Tensor(a!) act) -> ()", swiglu_fwd_into_);
   BLLM_OP("swiglu_bwd_lowrank(Tensor gu, Tensor base, Tensor u, Tensor P, float scale) -> Tensor", swiglu_bwd_lowrank);

@@ -166,7 +166,9 @@ def ragged_weights(a, m, cfg):
     """``--ragged B,... --weight_dtype fp8``: greedy ``generate_ragged`` on the model's weights
     against the fp8 decode weights, interleaved: ``fp8`` builds the packs inside every call (what a
     single ``generate_ragged`` call pays), ``fp8_prebuilt`` takes packs built once (what every
-    batch of ``generate_responses`` pays); ``pack_build_ms`` is that build."""
+    batch of ``generate_responses`` pays); ``pack_build_ms`` is that build.  ``--weight_dtype mxfp4``
+    runs three arms instead -- model weights, fp8 prebuilt, mxfp4 prebuilt -- and reports both
+    builds (``pack_build_ms`` fp8, ``pack_build_ms_mxfp4``)."""
     sizes = [int(b) for b in a.ragged.split(",")]
     prompts, tok_name = _alpaca_prompts(a.model, cfg, max(sizes))
     ctx = cfg.context_length
@@ -174,12 +176,20 @@ def ragged_weights(a, m, cfg):
     m.new_decode_weights("fp8")                         # warm-up of the build
     build = [_timed(lambda: m.new_decode_weights("fp8")) for _ in range(3)]
     packs = m.new_decode_weights("fp8")
+    w4 = a.weight_dtype == "mxfp4"
+    if w4:
+        m.new_decode_weights("mxfp4")
+        build4 = [_timed(lambda: m.new_decode_weights("mxfp4")) for _ in range(3)]
+        packs4 = m.new_decode_weights("mxfp4")
     rows = []
     for B in sizes:
         ps = prompts[:B]
         arms = {"model": lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv),
                 "fp8": lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv, weight_dtype="fp8"),
                 "fp8_prebuilt": lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv, weight_dtype=packs)}
+        if w4:
+            del arms["fp8"]
+            arms["mxfp4_prebuilt"] = lambda: G.generate_ragged(m, ps, a.tokens, ctx, kv_dtype=kv, weight_dtype=packs4)
         for fn in arms.values():
             fn()
         times = {k: [] for k in arms}
@@ -196,6 +206,10 @@ def ragged_weights(a, m, cfg):
                                    "ms_per_step_range": [round(ms[0], 4), round(ms[-1], 4)]}
         row["model_over_fp8_prebuilt"] = round(row["weights_model"]["ms_per_step"] /
                                                row["weights_fp8_prebuilt"]["ms_per_step"], 3)
+        if w4:
+            row["pack_build_ms_mxfp4"] = round(1000 * statistics.median(build4), 2)
+            row["fp8_prebuilt_over_mxfp4_prebuilt"] = round(row["weights_fp8_prebuilt"]["ms_per_step"] /
+                                                            row["weights_mxfp4_prebuilt"]["ms_per_step"], 3)
         print(json.dumps(row), flush=True)
         rows.append(row)
     if a.out:
@@ -356,7 +370,7 @@ def main():
     ap.add_argument("--kv_dtype", default="model", choices=["model", "fp8"],
                     help="--context: fp8 compares the KV-cache formats through generate_ragged (see above)")
     ap.add_argument("--kv_arms", default="model,fp8", help="--kv_dtype fp8: the arms to run")
-    ap.add_argument("--weight_dtype", default="model", choices=["model", "fp8"],
+    ap.add_argument("--weight_dtype", default="model", choices=["model", "fp8", "mxfp4"],
                     help="--ragged: fp8 compares the decode steps on fp8 weight packs with the model's weights")
     ap.add_argument("--lora_rank", type=int, default=0,
                     help="--weight_dtype fp8: a LoRA model (this rank on every linear, nonzero B), folded into the packs")
@@ -385,7 +399,7 @@ def main():
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
     if a.ragged and a.speculative:
         return ragged_speculative(a, m, cfg)
-    if a.ragged and a.weight_dtype == "fp8":
+    if a.ragged and a.weight_dtype in ("fp8", "mxfp4"):
         return ragged_weights(a, m, cfg)
     if a.ragged:
         return ragged_sampling(a, m, cfg) if a.temperature > 0 else ragged(a, m, cfg)

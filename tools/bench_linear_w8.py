@@ -10,7 +10,13 @@ shape and M one JSON line: median and range over ``--repeats`` of the microsecon
 (``--iters`` calls between two device synchronisations), the TB/s of the packed bytes (N K, what
 the fp8 kernel must read), and the ratio library / fp8.  The timings include the launch: at these
 sizes it is part of what a decode step pays.
-Usage: python tools/bench_linear_w8.py [--models llama3_2_1B,llama3_8B,gpt2_774M] [--rows 1,8,32] [--out FILE]"""
+
+``--format mxfp4`` adds a third arm to the same rotation, ``ops.linear_w4`` (csrc/linear_w4.hip) on
+the MXFP4 pack of the same weight (N K 17 / 32 bytes; C is then sized by these, the smallest), and
+reports its TB/s, the ratio fp8 / mxfp4 and ``w4_below_w8_range``: whether the MXFP4 median lies
+below every fp8 repeat.
+Usage: python tools/bench_linear_w8.py [--models llama3_2_1B,llama3_8B,gpt2_774M] [--rows 1,8,32] [--format mxfp4]
+       [--out FILE]"""
 import argparse
 import json
 import os
@@ -55,17 +61,23 @@ def main():
     ap.add_argument("--rows", default="1,8,32")
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--format", default="fp8", choices=["fp8", "mxfp4"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    w4 = a.format == "mxfp4"
     ops.load_ext(required=True)
     dt, dev = torch.bfloat16, "cuda"
     rows = []
     for model in a.models.split(","):
         for name, N, K, kind in SHAPES[model]:
-            C = -(-2 * LLC_BYTES // (N * K)) + 1
+            C = -(-2 * LLC_BYTES // (N * K * 17 // 32 if w4 else N * K)) + 1
             W = torch.randn(C, N, K, device=dev, dtype=dt) * 0.02
             pack = ops.w8_pack(W[0])
             packs = [pack] + [pack._replace(data=pack.data.clone()) for _ in range(C - 1)]
+            if w4:
+                pack4 = ops.w4_pack(W[0])
+                packs4 = [pack4] + [pack4._replace(data=pack4.data.clone(), scale=pack4.scale.clone())
+                                    for _ in range(C - 1)]
             bias = torch.randn(N, device=dev, dtype=dt)
             for M in (int(m) for m in a.rows.split(",")):
                 x = torch.randn(M, K, device=dev, dtype=dt)
@@ -79,6 +91,9 @@ def main():
                 else:
                     arms = {"library": lambda i: mm_nt(x, W[i % C]),
                             "linear_w8": lambda i: ops.linear_w8(x, packs[i % C])}
+                if w4:
+                    b4, r4 = (bias if kind == "bias" else None), (res if kind == "residual" else None)
+                    arms["linear_w4"] = lambda i: ops.linear_w4(x, packs4[i % C], b4, r4)
                 for fn in arms.values():
                     timed(fn, max(10, C))
                 us = {n: [] for n in arms}
@@ -92,9 +107,15 @@ def main():
                               "us_range": [round(min(us[n]), 2), round(max(us[n]), 2)]}
                 row["packed_TBps"] = round(N * K / row["linear_w8"]["us_per_call"] * 1e-6, 3)
                 row["library_over_w8"] = round(row["library"]["us_per_call"] / row["linear_w8"]["us_per_call"], 2)
+                if w4:
+                    row["w4_packed_TBps"] = round(N * K * 17 / 32 / row["linear_w4"]["us_per_call"] * 1e-6, 3)
+                    row["w8_over_w4"] = round(row["linear_w8"]["us_per_call"] / row["linear_w4"]["us_per_call"], 2)
+                    row["w4_below_w8_range"] = row["linear_w4"]["us_per_call"] < row["linear_w8"]["us_range"][0]
                 print(json.dumps(row), flush=True)
                 rows.append(row)
             del W, packs, pack
+            if w4:
+                del packs4, pack4
             torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
