@@ -58,6 +58,8 @@ def perform_checks(args):
                  or getattr(args, "generate_weight_dtype", "model") != "model"):
         raise ValueError("--generate_speculative runs on the default cache and weights: not with "
                          "--generate_kv_dtype fp8 or --generate_weight_dtype fp8 / mxfp4.")
+    if getattr(args, "generate_continuous", False) and spec:
+        raise ValueError("--generate_continuous does not speculate: not with --generate_speculative.")
     if not os.path.exists(args.data_dir) and not gen_only:   # --generate_only reads no training data
         if args.synthetic_data:
             os.makedirs(args.data_dir, exist_ok=True)
@@ -203,6 +205,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "the continuation of the latest earlier occurrence of the answer's last two tokens in its own "
                         "text; verified with the seeded sampler, so the answers are those of 0 (off) in fewer steps "
                         "where an answer quotes its prompt or repeats itself.  Needs K more free positions per prompt")
+    x.add_argument("--generate_continuous", action="store_true",
+                   help="continuous batching of --generate_prompts (train/generate.py:generate_continuous): "
+                        "--batch_size cache rows decode the whole list in input order, and a row whose answer is "
+                        "done takes the next prompt instead of idling until its batch's longest answer ends.  The "
+                        "same answers in fewer decode steps; composes with --generate_kv_dtype, "
+                        "--generate_weight_dtype and the sampler flags, not with --generate_speculative")
     x.add_argument("--generate_only", action="store_true",
                    help="no data preparation, training or final save: build the model (--load_weights / "
                         "--resume), answer --generate_prompts, exit")
@@ -294,6 +302,8 @@ def _generate_responses(trainer, args, rank, out_dir):
         sampling["weight_dtype"] = args.generate_weight_dtype
     if getattr(args, "generate_speculative", 0):
         sampling["speculative"] = args.generate_speculative
+    if getattr(args, "generate_continuous", False):
+        sampling["continuous"] = True
     responses = trainer.generate_responses(texts, args.generate_max_tokens, args.batch_size, **sampling)
     if rank != 0:
         return

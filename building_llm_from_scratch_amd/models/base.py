@@ -642,26 +642,44 @@ class BaseLM(nn.Module):
 
     # -- ragged batches: every row at its own position --------------------------------------
     @torch.no_grad()
-    def forward_prefill_ragged(self, idx_packed: torch.Tensor, seq: SeqPack, cache) -> torch.Tensor:
+    def forward_prefill_ragged(self, idx_packed: torch.Tensor, seq: SeqPack, cache, rows=None) -> torch.Tensor:
         """Prefill of a ragged batch: ``idx_packed`` [N] holds the prompts back to back, sequence b
         at rows [seq.bounds[b], seq.bounds[b+1]) (``pack_prompts``).  One unpadded pass
         (variable-length attention, positions from ``seq.pos_ids``) that fills rows 0 .. len_b - 1
         of ``cache`` row b; returns the logits [B, V] after each sequence's last token.  Call inside
-        ``engine.params_resident()`` like :meth:`forward_cached`."""
+        ``engine.params_resident()`` like :meth:`forward_cached`.
+
+        ``rows`` (host integers: a list or a CPU tensor, distinct and inside the cache's rows): the
+        pack holds ``len(rows)`` sequences, which may be fewer than the cache has rows, and
+        sequence i fills ``cache`` row ``rows[i]`` (admission of new prompts into a live cache,
+        train/generate.py:generate_continuous); the logits come back in the pack's order, [n, V].
+        Every other cache row, and every position of a filled row at or beyond its sequence's
+        length, stays as it is."""
+        from .. import ops
         self._ensure_flat()
         comps, rc = self._comps, self._rctx
         kc = cache[0][0]
         nseq = len(seq.bounds) - 1
-        if nseq != kc.shape[0] or seq.max_len > kc.shape[2]:
-            raise ValueError(f"ragged prefill: {nseq} sequences of at most {seq.max_len} tokens do not fit a cache "
-                             f"of {kc.shape[0]} rows x {kc.shape[2]} positions")
+        if rows is None:
+            if nseq != kc.shape[0] or seq.max_len > kc.shape[2]:
+                raise ValueError(f"ragged prefill: {nseq} sequences of at most {seq.max_len} tokens do not fit a "
+                                 f"cache of {kc.shape[0]} rows x {kc.shape[2]} positions")
+        else:
+            if seq.max_len > kc.shape[2]:
+                raise ValueError(f"ragged prefill: sequences of up to {seq.max_len} tokens do not fit a cache of "
+                                 f"{kc.shape[2]} positions")
+            rows = ops.CacheRows(rows, nseq, kc.shape[0], self._anchor.device, "ragged prefill")
         if min(b - a for a, b in zip(seq.bounds[:-1], seq.bounds[1:])) < 1:
             raise ValueError("ragged prefill: every sequence needs at least one token")
         rc.sync_all_params()
         idx = idx_packed.reshape(-1).to(self._anchor.device)
         x = comps[0].infer_ragged(idx, seq)
-        for c, kv in zip(comps[1:-1], cache):
-            x = c.infer_ragged(x, seq, kv)
+        if rows is None:
+            for c, kv in zip(comps[1:-1], cache):
+                x = c.infer_ragged(x, seq, kv)
+        else:
+            for c, kv in zip(comps[1:-1], cache):
+                x = c.infer_ragged(x, seq, kv, rows=rows)
         return comps[-1].infer_rows(x, (seq.cu[1:] - 1).to(torch.long))
 
     @torch.no_grad()

@@ -309,16 +309,17 @@ class LlamaBlockCompute(UnitCompute):
         return self._infer_out(x2d, ops.attn_decode_append_rows(qkv, kv[0], kv[1], pos_rows, H, G, scales=kv[2:]),
                                weights)
 
-    def infer_ragged(self, x2d, seq, kv):
+    def infer_ragged(self, x2d, seq, kv, rows=None):
         """Prefill of a ragged batch (packed rows, ``seq``: its SeqPack): variable-length attention,
-        and the rotated K / V of sequence b into rows 0 .. len_b - 1 of cache row b."""
+        and the rotated K / V of sequence b into rows 0 .. len_b - 1 of cache row b
+        (``rows``, an ``ops.CacheRows``: of cache row ``rows[b]``)."""
         cfg = self.rctx.cfg
         H, G, hd = cfg.n_heads, cfg.n_kv_groups, cfg.head_dim
         cos, sin = self.rctx.rope
         qkv = self._infer_qkv(x2d)
         ops.rope_pos_(qkv, cos, sin, seq.pos_ids, H, G, hd)
         o, _ = ops.flash_attn_varlen_fwd(qkv, seq.cu, seq.max_len, H, G, hd, bounds=seq.bounds)
-        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1], scales=kv[2:])
+        ops.kv_cache_fill_varlen(qkv, seq.cu, kv[0], kv[1], scales=kv[2:], rows=rows)
         return self._infer_out(x2d, o)
 
     def infer(self, x2d, B, t, pos, kv):

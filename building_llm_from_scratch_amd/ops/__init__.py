@@ -26,7 +26,7 @@ __all__ = [
     "flash_attn_varlen_bwd", "swiglu_fwd", "swiglu_bwd", "swiglu_bwd_act",
     "swiglu_bwd_lowrank_wgrad", "swiglu_bwd_lowrank_wgrad_ok",
     "gelu_fwd", "gelu_bwd", "gelu_bwd_bias", "gelu_bwd_act", "dropout_bwd_bias", "ce_fwd", "ce_bwd_", "embedding_fwd", "embedding_bwd",
-    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "attn_extend_rows", "spec_advance", "kv_cache_fill_varlen", "kv_quantize_rows", "kv_dequantize", "bias_grad_", "ext_available", "load_ext", "attention_backend",
+    "sq_norm_multi", "adamw_step_", "sample_rows", "attn_decode", "attn_decode_append_rows", "attn_extend_rows", "spec_advance", "kv_cache_fill_varlen", "CacheRows", "kv_quantize_rows", "kv_dequantize", "bias_grad_", "ext_available", "load_ext", "attention_backend",
     "lora_down", "lora_up_", "lora_wgrad", "lora_pack_t", "lora_kernel_ok", "lora_kernel_ok_dims",
     "lora_down_into", "lora_block_", "rmsnorm_fwd_into", "swiglu_fwd_into", "sum_partials_",
     "wgrad_gemm_", "wgrad_gemm_ok", "wgrad_gemm_enabled", "wgrad_gemm_preferred", "wgrad_splits",
@@ -411,7 +411,33 @@ def sample_rows(logits, stream, ctr, seed: int, temperature: float, top_k: int =
                            next_idx, out, finished, thr)
 
 
-def kv_cache_fill_varlen(qkv, cu, kc, vc, scales=None):
+class CacheRows:
+    """The ``rows=`` of ``kv_cache_fill_varlen``, checked and uploaded once: ``host`` (a list of
+    ints) and ``dev`` (int32 [n] on ``device``).  ``rows``: host integers, a list / tuple or a CPU
+    integer tensor -- the admission that picks them is host-driven, so the check costs no device
+    sync: exactly ``nseq`` of them, distinct, each inside [0, cache_rows) (ValueError otherwise).
+    A model builds one per prefill and hands it to every block's fill."""
+
+    def __init__(self, rows, nseq: int, cache_rows: int, device, name: str = "kv_cache_fill_varlen"):
+        if isinstance(rows, torch.Tensor):
+            if rows.device.type != "cpu" or rows.is_floating_point() or rows.dtype == torch.bool or rows.dim() != 1:
+                raise ValueError(f"{name}: rows must be host integers (a list or a 1-D CPU integer tensor), got "
+                                 f"{rows.dtype} {tuple(rows.shape)} on {rows.device}")
+            rows = rows.tolist()
+        elif not isinstance(rows, (list, tuple)) or any(isinstance(r, bool) or not isinstance(r, int) for r in rows):
+            raise ValueError(f"{name}: rows must be host integers (a list or a 1-D CPU integer tensor), got {rows!r}")
+        rows = list(rows)
+        if len(rows) != nseq:
+            raise ValueError(f"{name}: rows must name one cache row per sequence ({nseq}), got {len(rows)}")
+        if any(not 0 <= r < cache_rows for r in rows):
+            raise ValueError(f"{name}: rows {rows} must lie inside the cache's {cache_rows} rows")
+        if len(set(rows)) != len(rows):
+            raise ValueError(f"{name}: rows {rows} must be distinct")
+        self.host = rows
+        self.dev = torch.tensor(rows, dtype=torch.int32).to(device)
+
+
+def kv_cache_fill_varlen(qkv, cu, kc, vc, scales=None, rows=None):
     """Fill the caches [B, G, Tmax, hd] from a packed batch: sequence b is rows [cu[b], cu[b+1]) of
     qkv [N, (H+2G)*hd] (``cu`` int32 [B + 1] on qkv's device, every length <= Tmax -- the caller
     checks its host bounds); cache rows (b, g, t < len_b) get the K/V of row cu[b] + t, every
@@ -419,20 +445,38 @@ def kv_cache_fill_varlen(qkv, cu, kc, vc, scales=None):
     vectors; any other head dim goes to the oracle).
 
     ``scales=(Ks, Vs)``: an fp8 cache (see ``attn_decode_append_rows``); the rows are quantised on
-    the way in and their scales written, in one launch for bf16 / fp16 with head dim 64 / 128."""
+    the way in and their scales written, in one launch for bf16 / fp16 with head dim 64 / 128.
+
+    ``rows`` (host integers: a list, a CPU tensor, or a :class:`CacheRows` made from them): the
+    slot-mapped fill.  The batch has ``n = len(cu) - 1`` sequences, which may be fewer than the
+    cache has rows, and sequence i goes to cache row ``rows[i]`` instead of row i.  The rows are
+    checked here on the host -- distinct, inside the cache, exactly n -- and uploaded as one int32
+    vector; every cache element not addressed (other rows, positions at or beyond a sequence's
+    length) stays as it is.  ``None``: the launch described above, unchanged."""
+    if rows is not None and not isinstance(rows, CacheRows):
+        rows = CacheRows(rows, cu.numel() - 1, kc.shape[0], qkv.device)
+    elif rows is not None and (len(rows.host) != cu.numel() - 1 or max(rows.host, default=-1) >= kc.shape[0]):
+        raise ValueError(f"kv_cache_fill_varlen: rows {rows.host} do not go with {cu.numel() - 1} sequences and a "
+                         f"cache of {kc.shape[0]} rows")
     sc = _fp8_scales("kv_cache_fill_varlen", kc, vc, scales)
     if sc is not None:
         if _decode_kernel(qkv, kc.shape[3]):
             load_ext(required=True)
-            _k().kv_cache_fill_varlen_fp8(qkv, cu, kc, sc[0], vc, sc[1])
+            if rows is None:
+                _k().kv_cache_fill_varlen_fp8(qkv, cu, kc, sc[0], vc, sc[1])
+            else:
+                _k().kv_cache_fill_varlen_fp8(qkv, cu, kc, sc[0], vc, sc[1], rows.dev)
             return
-        ref.kv_cache_fill_varlen_fp8(qkv, cu, kc, vc, sc[0], sc[1])
+        ref.kv_cache_fill_varlen_fp8(qkv, cu, kc, vc, sc[0], sc[1], rows=None if rows is None else rows.host)
         return
     if qkv.device.type == "cuda" and (kc.shape[3] * kc.element_size()) % 16 == 0:
         load_ext(required=True)
-        _k().kv_cache_fill_varlen(qkv, cu, kc, vc)
+        if rows is None:
+            _k().kv_cache_fill_varlen(qkv, cu, kc, vc)
+        else:
+            _k().kv_cache_fill_varlen(qkv, cu, kc, vc, rows.dev)
         return
-    ref.kv_cache_fill_varlen(qkv, cu, kc, vc)
+    ref.kv_cache_fill_varlen(qkv, cu, kc, vc, rows=None if rows is None else rows.host)
 
 
 def bias_grad_(dy, db, accumulate: bool = False):

@@ -629,16 +629,18 @@ def spec_advance(idx, samp, hist, h0, pos, ctr, nsteps, finished, out, eos_id: i
         idx[b] = torch.tensor(row, dtype=idx.dtype, device=idx.device)
 
 
-def kv_cache_fill_varlen(qkv, cu, kcache, vcache):
+def kv_cache_fill_varlen(qkv, cu, kcache, vcache, rows=None):
     """Reference for the cache prefill from a packed batch: sequence b is rows [cu[b], cu[b+1]) of
-    qkv [N, (H+2G)*hd]; cache rows (b, g, t < len_b) <- the k / v of row cu[b] + t."""
+    qkv [N, (H+2G)*hd]; cache rows (b, g, t < len_b) <- the k / v of row cu[b] + t.  ``rows``
+    (host ints, one per sequence): sequence b goes to cache row ``rows[b]`` instead of row b."""
     G, hd = kcache.shape[1], kcache.shape[3]
-    rows = qkv.view(qkv.shape[0], -1, hd)
-    H = rows.shape[1] - 2 * G
+    packed = qkv.view(qkv.shape[0], -1, hd)
+    H = packed.shape[1] - 2 * G
     cb = varlen_bounds(cu)
-    for b, (r0, r1) in enumerate(zip(cb[:-1], cb[1:])):
-        kcache[b, :, :r1 - r0] = rows[r0:r1, H:H + G].transpose(0, 1)
-        vcache[b, :, :r1 - r0] = rows[r0:r1, H + G:].transpose(0, 1)
+    dst = range(len(cb) - 1) if rows is None else [int(r) for r in rows]
+    for b, r0, r1 in zip(dst, cb[:-1], cb[1:]):
+        kcache[b, :, :r1 - r0] = packed[r0:r1, H:H + G].transpose(0, 1)
+        vcache[b, :, :r1 - r0] = packed[r0:r1, H + G:].transpose(0, 1)
 
 
 # ------------------------------------------------------------------ FP8 KV cache (csrc/attn_decode_fp8.hip oracle)
@@ -682,15 +684,16 @@ def attn_decode_append_rows_fp8(qkv, k8, v8, kscale, vscale, pos, H: int, G: int
     return out
 
 
-def kv_cache_fill_varlen_fp8(qkv, cu, k8, v8, kscale, vscale):
+def kv_cache_fill_varlen_fp8(qkv, cu, k8, v8, kscale, vscale, rows=None):
     """``kv_cache_fill_varlen`` into an fp8 cache: rows (b, g, t < len_b) and their scales <- the
-    quantised k / v of packed row cu[b] + t; nothing else is written."""
+    quantised k / v of packed row cu[b] + t; nothing else is written.  ``rows``: as there."""
     G, hd = k8.shape[1], k8.shape[3]
-    rows = qkv.view(qkv.shape[0], -1, hd)
-    H = rows.shape[1] - 2 * G
+    packed = qkv.view(qkv.shape[0], -1, hd)
+    H = packed.shape[1] - 2 * G
     cb = varlen_bounds(cu)
-    for b, (r0, r1) in enumerate(zip(cb[:-1], cb[1:])):
-        for c8, cs, src in ((k8, kscale, rows[r0:r1, H:H + G]), (v8, vscale, rows[r0:r1, H + G:])):
+    dst = range(len(cb) - 1) if rows is None else [int(r) for r in rows]
+    for b, r0, r1 in zip(dst, cb[:-1], cb[1:]):
+        for c8, cs, src in ((k8, kscale, packed[r0:r1, H:H + G]), (v8, vscale, packed[r0:r1, H + G:])):
             q, s = kv_quantize_rows(src.transpose(0, 1))
             c8[b, :, :r1 - r0] = q
             cs[b, :, :r1 - r0] = s

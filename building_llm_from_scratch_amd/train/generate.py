@@ -543,6 +543,216 @@ def _speculate(model, cache, prompts, lens, hints, K: int, first, pos, ctr, fini
     return new
 
 
+@torch.no_grad()
+def generate_continuous(model, prompts, max_new_tokens, context_size: int, slots: int, eos_id: Optional[int] = None,
+                        temperature: float = 0.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                        seed: Optional[int] = None, streams=None, kv_dtype: Optional[str] = None, weight_dtype=None,
+                        stats: Optional[dict] = None) -> list:
+    """Continuous batching: :func:`generate_ragged`'s answers for a prompt list of any length from
+    ``slots`` cache rows that never idle -- a row whose answer is done is handed to the next
+    waiting prompt while the others keep decoding.  Returns one 1-D tensor per prompt, the prompt
+    followed by its answer, cut before the first ``eos_id``.
+
+    ``max_new_tokens``: an int, or one int per prompt (prompt i draws at most ``n_i`` tokens; with
+    ``n_i == 0`` it comes back as it is and never takes a slot).  The device sampler
+    ``ops.sample_rows`` is the only sampler (there is no ``generator`` argument): prompt i draws
+    from stream ``streams[i]`` (default i) with its own token counter, so its answer is a function
+    of (seed, stream, its logits) and does not depend on the slot it ran in, on when it was
+    admitted or on its neighbours, up to GEMM rounding of the logits.  Without ``seed`` the call
+    runs ``seed = 0`` at temperature 0, the argmax.  ``kv_dtype`` / ``weight_dtype``: as in
+    :func:`generate_ragged` -- every admission prefill runs on the model's own weights, every
+    decode step on the packs.  No speculation here.
+
+    One cache of ``slots`` rows x ``context_size`` positions is allocated once; where
+    ``decode_graph_ok`` holds one :class:`RowsDecodeGraph` (forward + sampler + position increment)
+    is captured after the first admission and replayed for the whole call, elsewhere (CPU, fp32,
+    ``BLLM_DECODE_GRAPH=0``) the same loop runs the step eagerly.  Parameters stay resident.
+
+    The schedule.  E = ``EOS_CHECK_EVERY``; d = tokens an occupied slot has drawn, known on the host
+    without a read: 1 after admission, + 1 per replay; n = its prompt's budget.  Repeat:
+
+    1. Admit.  While slots are free and prompts wait, the lowest free slot takes the next prompt in
+       the caller's order.  A round's admissions are one packed prefill
+       (``forward_prefill_ragged(..., rows=)``), one ``sample_rows`` over its [n, V] logits (the
+       prompts' streams, counters 0) and a scatter into the slot state: next token, position =
+       prompt length, counter = 1, stream id, finished flag, column 0 of the slot's output row.
+    2. Run.  ``run = min(E, min over occupied slots of (n - d))`` replays (or eager steps).
+    3. Look.  With ``eos_id``, the occupied slots' finished flags are read once.
+    4. Retire every occupied slot with ``d == n`` or its flag set: its output row is copied out;
+       the answer is the tokens before the first eos, at most n.
+    5. Park.  Free slots nothing waits for keep stepping (the graph has ``slots`` rows): before
+       every run their position and counter are rewritten to 0.
+    6. Stop when no slot is occupied and no prompt waits.
+
+    Invariants.  (a) A slot's position stays below ``len + n <= context_size <= `` the model's
+    context (entry check; step 2 never runs a slot past d = n; a parked slot restarts from 0 and
+    ``run < context_size``), so no cache row or position-table entry out of range is touched.
+    (b) No answer token is overwritten: a slot writes output column d - 1 < n once, and is not
+    stepped past its budget (the sampler's column clamp never acts on an occupied slot).  (c) A new
+    occupant never sees its predecessor: it attends over keys 0..pos only; the admission fill
+    rewrote positions below its prompt length and each later position is appended before it is
+    read.  (d) The kernels, :class:`RowsDecodeGraph`, :func:`generate_ragged` and
+    :func:`generate_cached` are used as they are.
+
+    ``stats`` (a dict) receives ``replays``, ``prefills`` and per prompt ``steps`` (replays while it
+    held a slot), ``slot`` (None: never took one) and ``new_tokens`` (tokens of its answer, its eos
+    included when it drew one).
+
+    ValueError before any work: ``slots < 1``; a budget list of the wrong length or a negative
+    budget; an empty prompt; ``len + n_i > context_size``; ``context_size`` beyond the model's;
+    a temperature without ``seed``."""
+    from .. import ops
+    from ..models.base import DecodeWeights, pack_prompts
+    fn = "generate_continuous"
+    if kv_dtype not in (None, "fp8"):
+        raise ValueError(f"{fn}: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+    if weight_dtype is not None and weight_dtype not in ("fp8", "mxfp4") and not isinstance(weight_dtype, DecodeWeights):
+        raise ValueError(f"{fn}: weight_dtype must be None, 'fp8', 'mxfp4' or the model's new_decode_weights(), got "
+                         f"{weight_dtype!r}")
+    if isinstance(slots, bool) or not isinstance(slots, int) or slots < 1:
+        raise ValueError(f"{fn}: slots must be an int >= 1, got {slots!r}")
+    if not isinstance(prompts, (list, tuple)) or len(prompts) == 0:
+        raise ValueError(f"{fn}: prompts must be a non-empty list of 1-D token tensors")
+    for b, p in enumerate(prompts):
+        if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() == 0 or p.dtype != torch.long:
+            raise ValueError(f"{fn}: prompt {b} must be a non-empty 1-D LongTensor")
+    P = len(prompts)
+    lens = [int(p.numel()) for p in prompts]
+    if isinstance(max_new_tokens, (list, tuple)):
+        budgets = list(max_new_tokens)
+        if len(budgets) != P:
+            raise ValueError(f"{fn}: max_new_tokens must be an int or one int per prompt ({P}), got {len(budgets)}")
+    else:
+        budgets = [max_new_tokens] * P
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 0 for n in budgets):
+        raise ValueError(f"{fn}: every budget must be an int >= 0, got {max_new_tokens!r}")
+    for b in range(P):
+        if lens[b] + budgets[b] > context_size:
+            raise ValueError(f"{fn}: prompt {b} ({lens[b]} tokens) + its budget ({budgets[b]}) exceeds context_size "
+                             f"({context_size}); this path has no sliding window")
+    if context_size > model.cfg.context_length:
+        raise ValueError(f"{fn}: context_size ({context_size}) exceeds the model's context length "
+                         f"({model.cfg.context_length})")
+    if seed is None:
+        if float(temperature) != 0.0:
+            raise ValueError(f"{fn}: the seeded device sampler is the only one here; pass seed=... with a temperature")
+        seed, top_k, top_p = 0, None, None   # greedy through the device sampler: at temperature 0 it is the argmax
+    top_k, top_p, stream_ids = _sampler_args(fn, P, temperature, top_k, top_p, seed, streams)
+    device = next(model.parameters()).device
+    E = max(EOS_CHECK_EVERY, 1)
+    eos = -1 if eos_id is None else int(eos_id)
+    maxn = max(budgets)
+    st = {"replays": 0, "prefills": 0, "steps": [0] * P, "slot": [None] * P, "new_tokens": [0] * P}
+    gens = [None] * P                           # per prompt: its output row's first n_i columns, on the device
+    waiting = [i for i in range(P) if budgets[i] > 0]
+    was_training = model.training
+    model.eval()
+    eng = model.rctx.engine
+    resident = eng.params_resident() if hasattr(eng, "params_resident") else _null()
+    with resident:
+        if waiting:
+            cache = model.new_kv_cache(slots, context_size) if kv_dtype is None else \
+                model.new_kv_cache(slots, context_size, kv_dtype=kv_dtype)
+            kw = {}
+            if weight_dtype is not None:
+                kw["weights"] = model.new_decode_weights(weight_dtype) if isinstance(weight_dtype, str) \
+                    else weight_dtype
+            # the slot state, all on the device and read by the replayed step
+            nxt = torch.zeros(slots, 1, dtype=torch.long, device=device)      # next input token
+            pos = torch.zeros(slots, dtype=torch.int32, device=device)        # next position
+            ctr = torch.zeros(slots, dtype=torch.int32, device=device)        # tokens drawn = next output column
+            stream_t = torch.zeros(slots, dtype=torch.long, device=device)
+            finished = torch.zeros(slots, dtype=torch.bool, device=device)
+            out = torch.zeros(slots, maxn, dtype=torch.long, device=device)
+
+            def draw(lg, nx):
+                return ops.sample_rows(lg.contiguous(), stream_t, ctr, seed, temperature, top_k, top_p, eos_id=eos,
+                                       next_idx=nx, out=out, finished=finished)
+
+        dec = None
+        occ = {}                                # slot -> [prompt, d]
+        parked, parked_t = None, None
+        head = 0
+        while occ or head < len(waiting):
+            # 1. admit
+            free = [s for s in range(slots) if s not in occ]
+            adm = []
+            while free and head < len(waiting):
+                adm.append((free.pop(0), waiting[head]))
+                head += 1
+            if adm:
+                rows = [s for s, _ in adm]
+                idx, seq = pack_prompts([prompts[i] for _, i in adm], device)
+                logits = model.forward_prefill_ragged(idx, seq, cache, rows=rows)
+                meta = torch.tensor([rows, [lens[i] for _, i in adm], [stream_ids[i] for _, i in adm]],
+                                    dtype=torch.long).to(device)
+                fin = torch.zeros(len(adm), dtype=torch.bool, device=device)
+                tok = ops.sample_rows(logits.contiguous(), meta[2].contiguous(),
+                                      torch.zeros(len(adm), dtype=torch.int32, device=device), seed, temperature,
+                                      top_k, top_p, eos_id=eos, finished=fin)
+                nxt.index_copy_(0, meta[0], tok[:, None])
+                pos.index_copy_(0, meta[0], meta[1].to(torch.int32))
+                ctr.index_fill_(0, meta[0], 1)
+                stream_t.index_copy_(0, meta[0], meta[2])
+                finished.index_copy_(0, meta[0], fin)
+                out[:, 0].index_copy_(0, meta[0], tok)
+                for s, i in adm:
+                    occ[s] = [i, 1]
+                    st["slot"][i] = s
+                st["prefills"] += 1
+                if dec is None and maxn > 8 and _graph_enabled() and model.decode_graph_ok(cache):
+                    dec = RowsDecodeGraph(model, cache, pos, device, sampler=draw, **kw)
+                    dec.idx.copy_(nxt)
+                    nxt, pos = dec.idx, dec.pos     # the captured step reads and advances these
+            # 2. run (5: free slots restart from position and counter 0)
+            run = min(E, min(budgets[i] - d for i, d in occ.values()))
+            if run > 0:
+                free = [s for s in range(slots) if s not in occ]
+                if free:
+                    if free != parked:
+                        parked, parked_t = free, torch.tensor(free, dtype=torch.long).to(device)
+                    pos.index_fill_(0, parked_t, 0)
+                    ctr.index_fill_(0, parked_t, 0)
+                for _ in range(run):
+                    if dec is not None:
+                        dec.replay()
+                    else:
+                        logits = model.forward_cached_rows(nxt, cache, pos, **kw)
+                        pos += 1
+                        draw(logits, nxt)
+                st["replays"] += run
+                for v in occ.values():
+                    v[1] += run
+            # 3. look
+            flags = finished.tolist() if eos_id is not None else None
+            # 4. retire
+            for s in sorted(occ):
+                i, d = occ[s]
+                if d == budgets[i] or (flags is not None and flags[s]):
+                    gens[i] = out[s, :d].clone()
+                    st["steps"][i] = d - 1
+                    del occ[s]
+        # the cut before each answer's first eos: one host read for the whole call
+        keep = [0 if g is None else int(g.numel()) for g in gens]
+        if eos_id is not None and any(keep):
+            flat = (torch.cat([g for g in gens if g is not None]) == eos_id).tolist()
+            o = 0
+            for i in range(P):
+                row = flat[o:o + keep[i]]
+                o += keep[i]
+                if True in row:
+                    keep[i] = row.index(True)
+                    st["new_tokens"][i] = keep[i] + 1
+                else:
+                    st["new_tokens"][i] = keep[i]
+        else:
+            st["new_tokens"] = list(keep)
+    model.train(was_training)
+    if stats is not None:
+        stats.update(st)
+    return [p.to(device) if g is None else torch.cat((p.to(device), g[:k])) for p, g, k in zip(prompts, gens, keep)]
+
+
 class _null:
     def __enter__(self):
         return self

@@ -33,7 +33,7 @@ from ..utils.misc import read_json_file, read_text_file, text_to_token_ids, toke
 from ..data.datasets import unpad_lengths
 from ..data.loaders import first_batches
 from .checkpoint import resume_state_path, save_model, save_resume_state
-from .generate import generate_cached, generate_ragged
+from .generate import generate_cached, generate_continuous, generate_ragged
 
 IGNORE_INDEX = -100   # the instruction collate's masked-target id (data/datasets.py)
 
@@ -496,7 +496,8 @@ class Trainer:
         return decoded
 
     def generate_responses(self, prompts, max_new_tokens: int, batch_size: int, temperature: float = 0.0,
-                           top_k=None, top_p=None, seed=None, kv_dtype=None, weight_dtype=None, speculative=None):
+                           top_k=None, top_p=None, seed=None, kv_dtype=None, weight_dtype=None, speculative=None,
+                           continuous: bool = False):
         """Continuations of ``prompts`` (strings, tokenised with the run's tokenizer), in input
         order, each cut before its first eos: greedy by default; with ``seed`` sampled on the
         device (``temperature``, ``top_k``, ``top_p``: :func:`generate_ragged`), prompt i drawing
@@ -512,7 +513,15 @@ class Trainer:
         across calls: the weights may change in between).  ``speculative=K``: exact speculative
         decoding with K prompt-lookup drafts per step (:func:`generate_ragged`): the same answers
         in fewer steps where an answer repeats its prompt or itself; prompt i keeps stream i, and
-        a prompt must leave K more positions free."""
+        a prompt must leave K more positions free.  ``continuous=True``: continuous batching --
+        the whole list is ONE :func:`generate_continuous` call with ``batch_size`` slots, the prompts
+        in input order (nothing is padded, so nothing is sorted), prompt i on stream i: a slot whose
+        answer is done takes the next prompt instead of idling until its batch's longest answer
+        ends.  The same answers up to GEMM rounding, in fewer decode steps; not with
+        ``speculative``."""
+        if continuous and speculative:
+            raise ValueError("generate_responses: continuous batching does not speculate (continuous=True with "
+                             "speculative=K)")
         if weight_dtype not in (None, "fp8", "mxfp4"):
             raise ValueError(f"generate_responses: weight_dtype must be None, 'fp8' or 'mxfp4', got {weight_dtype!r}")
         tok, cfg = self.loaderObj.tokenizer, self.config
@@ -534,6 +543,12 @@ class Trainer:
             eng = self.model.rctx.engine
             with eng.params_resident() if hasattr(eng, "params_resident") else contextlib.nullcontext():
                 weights = self.model.new_decode_weights(weight_dtype)
+        if continuous:
+            sampling = {} if seed is None else dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+            res = generate_continuous(self.model, ids, max_new_tokens, ctx, max(1, int(batch_size)),
+                                      eos_id=cfg["eos_id"], streams=list(range(len(ids))), kv_dtype=kv_dtype,
+                                      weight_dtype=weights, **sampling)
+            return [tok.decode(r[t.numel():].tolist()) for t, r in zip(ids, res)]
         for s in range(0, len(order), max(1, int(batch_size))):
             rows = order[s:s + max(1, int(batch_size))]
             sampling = {} if seed is None else dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,

@@ -147,9 +147,11 @@ void attn_decode(DType dt, const void* q, const void* kc, const void* vc, void* 
 void attn_decode_append_rows(DType dt, const void* qkv, void* kc, void* vc, void* out, const int* pos, int B, int H,
                              int G, int hd, int Tmax, hipStream_t s);
 // caches from a packed variable-length batch: cache row (b, g, t) <- k / v of qkv row cu[b] + t
-// (cu int32 [B + 1] on the device, every length <= Tmax); row_bytes = hd * element size, whole 16 B
+// (cu int32 [B + 1] on the device, every length <= Tmax); row_bytes = hd * element size, whole 16 B.
+// rows (int32 [B] on the device, or null): sequence b goes to cache row rows[b] of a cache with CB
+// rows instead of row b; the caller has checked them distinct and inside [0, CB)
 void kv_cache_fill_varlen(const void* qkv, const int* cu, void* kc, void* vc, long N, int B, int H, int G, int Tmax,
-                          int row_bytes, hipStream_t s);
+                          int row_bytes, hipStream_t s, const int* rows = nullptr, int CB = 0);
 
 // attn_decode_split.hip — the same attention in two launches (per key chunk, then a merge), for
 // caches of any length.  ws: fp32 scratch of attn_decode_split_workspace(B, H, hd, Tmax) floats,
@@ -179,9 +181,10 @@ void attn_extend_rows(DType dt, const void* qkv, void* kc, void* vc, void* out, 
 // attn_decode_fp8.hip -- the KV cache as e4m3fn bytes k8 / v8 [B, G, Tmax, hd] with one fp32 scale per
 // (row, kv head, position) ks / vs [B, G, Tmax]; dt is the dtype of qkv and out (bf16 / fp16), hd 64 / 128.
 // fill: kv_cache_fill_varlen, quantising.  decode: per-row append + attention in split-KV form for
-// any Tmax (ws and the grid limits of attn_decode_split.hip), two launches.
+// any Tmax (ws and the grid limits of attn_decode_split.hip), two launches.  rows / CB: as above.
 void kv_cache_fill_varlen_fp8(DType dt, const void* qkv, const int* cu, void* k8, float* ks, void* v8, float* vs,
-                              long N, int B, int H, int G, int hd, int Tmax, hipStream_t s);
+                              long N, int B, int H, int G, int hd, int Tmax, hipStream_t s,
+                              const int* rows = nullptr, int CB = 0);
 void attn_decode_append_rows_fp8(DType dt, const void* qkv, void* k8, float* ks, void* v8, float* vs, void* out,
                                  float* ws, const int* pos, int B, int H, int G, int hd, int Tmax, hipStream_t s);
 

@@ -56,27 +56,27 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_rows_k(const T* __res
 // of packed row cu[b] + t.  One thread per 16-B chunk of one (row, k-or-v head); the row's
 // sequence is found by bisection of cu (B + 1 entries, read through the scalar cache).  C =
 // chunks per head row, qsc = chunks per qkv row.  Any element type: the copy is bitwise.
+// Two forms share one body (kv_fill_body.h), as the decode kernels above do.  FILL_ROWS (slot-mapped
+// fill, admission into a live cache): the batch has B sequences and sequence b goes to cache row
+// rows[b] of a cache with CB rows, B <= CB; the host wrapper has checked the rows distinct and in
+// range, so no two threads store to one address.  Without it: row b, the kernel as it always was.
 __global__ __launch_bounds__(256) void kv_cache_fill_varlen_k(const uint4* __restrict__ qkv,
                                                               const int* __restrict__ cu, uint4* __restrict__ kc,
                                                               uint4* __restrict__ vc, long N, int B, int H, int G,
                                                               int Tmax, int C, long qsc) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long per_row = 2L * G * C;
-  if (i >= N * per_row) return;
-  const long n = i / per_row;
-  const int j = (int)((i % per_row) / C), c = (int)(i % C);  // j: k heads 0..G-1, then v heads
-  if (n < cu[0] || n >= cu[B]) return;                        // rows outside every sequence
-  int lo = 0, hi = B;                                         // cu[lo] <= n < cu[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (cu[mid] <= n) lo = mid; else hi = mid;
-  }
-  const int t = (int)(n - cu[lo]);
-  BLLM_DASSERT(t < Tmax, DBG_DECODE_POS);
-  if (t >= Tmax) return;
-  const int g = j < G ? j : j - G;
-  uint4* dst = (j < G ? kc : vc) + (((long)lo * G + g) * Tmax + t) * C + c;
-  *dst = qkv[n * qsc + (long)(H + j) * C + c];
+#define FILL_ROWS 0
+#include "kv_fill_body.h"
+#undef FILL_ROWS
+}
+
+__global__ __launch_bounds__(256) void kv_cache_fill_varlen_rows_k(const uint4* __restrict__ qkv,
+                                                                   const int* __restrict__ cu, uint4* __restrict__ kc,
+                                                                   uint4* __restrict__ vc, long N, int B, int H, int G,
+                                                                   int Tmax, int C, long qsc,
+                                                                   const int* __restrict__ rows, int CB) {
+#define FILL_ROWS 1
+#include "kv_fill_body.h"
+#undef FILL_ROWS
 }
 
 int attn_decode_max_len() { return DEC_MAXL; }
@@ -126,12 +126,17 @@ void attn_decode_append_rows(DType dt, const void* qkv, void* kc, void* vc, void
 }
 
 void kv_cache_fill_varlen(const void* qkv, const int* cu, void* kc, void* vc, long N, int B, int H, int G, int Tmax,
-                          int row_bytes, hipStream_t s) {
+                          int row_bytes, hipStream_t s, const int* rows, int CB) {
   const int C = row_bytes / 16;
   const long total = N * 2L * G * C;
   if (total == 0) return;
-  hipLaunchKernelGGL(kv_cache_fill_varlen_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     (const uint4*)qkv, cu, (uint4*)kc, (uint4*)vc, N, B, H, G, Tmax, C, (long)(H + 2 * G) * C);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (rows)
+    hipLaunchKernelGGL(kv_cache_fill_varlen_rows_k, grid, dim3(256), 0, s, (const uint4*)qkv, cu, (uint4*)kc,
+                       (uint4*)vc, N, B, H, G, Tmax, C, (long)(H + 2 * G) * C, rows, CB);
+  else
+    hipLaunchKernelGGL(kv_cache_fill_varlen_k, grid, dim3(256), 0, s, (const uint4*)qkv, cu, (uint4*)kc, (uint4*)vc,
+                       N, B, H, G, Tmax, C, (long)(H + 2 * G) * C);
 }
 
 }  // namespace bllm

@@ -60,53 +60,44 @@ __device__ __forceinline__ uint32_t f8_pair<f16_t, true>(uint32_t w) {
 // ------------------------------------------------------------------ fill
 // thread = (packed row n, k-or-v head j, 16-B piece c of its hd elements); C = HD / 8 lanes share a
 // head row (C divides 64, so a row never straddles a wave and its lanes leave together)
+// Two forms share one body (kv_fill_fp8_body.h).  FILL_ROWS: the slot-mapped form, as
+// kv_cache_fill_varlen_rows_k (sequence b of B -> cache row rows[b] of CB); without it the kernel
+// as it always was.
 template <typename T, int HD>
 __global__ __launch_bounds__(256) void kv_cache_fill_varlen_fp8_k(const T* __restrict__ qkv,
                                                                   const int* __restrict__ cu, uint8_t* __restrict__ k8,
                                                                   float* __restrict__ ks, uint8_t* __restrict__ v8,
                                                                   float* __restrict__ vs, long N, int B, int H, int G,
                                                                   int Tmax) {
-  constexpr int C = HD / 8;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long per_row = 2L * G * C;
-  if (i >= N * per_row) return;
-  const long n = i / per_row;
-  const int j = (int)((i % per_row) / C), c = (int)(i % C);  // j: k heads 0..G-1, then v heads
-  if (n < cu[0] || n >= cu[B]) return;                        // rows outside every sequence
-  int lo = 0, hi = B;                                         // cu[lo] <= n < cu[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (cu[mid] <= n) lo = mid; else hi = mid;
-  }
-  const int t = (int)(n - cu[lo]);
-  BLLM_DASSERT(t < Tmax, DBG_DECODE_POS);
-  if (t >= Tmax) return;
-  const Vec16<T> x = ld16(qkv + n * (long)(H + 2 * G) * HD + (long)(H + j) * HD + c * 8);
-  float f[8], a = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    f[e] = to_f(x.v[e]);
-    a = fmaxf(a, fabsf(f[e]));
-  }
-#pragma unroll
-  for (int o = C / 2; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-  const float s = f8_scale(a);
-  uint2 w;
-  w.x = f8_pack2(f[0], f[1], s) | (f8_pack2(f[2], f[3], s) << 16);
-  w.y = f8_pack2(f[4], f[5], s) | (f8_pack2(f[6], f[7], s) << 16);
-  const int g = j < G ? j : j - G;
-  const long row = ((long)lo * G + g) * Tmax + t;
-  *reinterpret_cast<uint2*>((j < G ? k8 : v8) + row * HD + c * 8) = w;
-  if (c == 0) (j < G ? ks : vs)[row] = s;
+#define FILL_ROWS 0
+#include "kv_fill_fp8_body.h"
+#undef FILL_ROWS
+}
+
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void kv_cache_fill_varlen_fp8_rows_k(
+    const T* __restrict__ qkv, const int* __restrict__ cu, uint8_t* __restrict__ k8, float* __restrict__ ks,
+    uint8_t* __restrict__ v8, float* __restrict__ vs, long N, int B, int H, int G, int Tmax,
+    const int* __restrict__ rows, int CB) {
+#define FILL_ROWS 1
+#include "kv_fill_fp8_body.h"
+#undef FILL_ROWS
 }
 
 void kv_cache_fill_varlen_fp8(DType dt, const void* qkv, const int* cu, void* k8, float* ks, void* v8, float* vs,
-                              long N, int B, int H, int G, int hd, int Tmax, hipStream_t s) {
+                              long N, int B, int H, int G, int hd, int Tmax, hipStream_t s, const int* rows, int CB) {
   const long total = N * 2L * G * (hd / 8);
   if (total == 0) return;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define L_(TT, HDD) hipLaunchKernelGGL((kv_cache_fill_varlen_fp8_k<TT, HDD>), grid, block, 0, s, (const TT*)qkv, cu, \
-                                       (uint8_t*)k8, ks, (uint8_t*)v8, vs, N, B, H, G, Tmax)
+#define L_(TT, HDD)                                                                                                \
+  do {                                                                                                             \
+    if (rows)                                                                                                      \
+      hipLaunchKernelGGL((kv_cache_fill_varlen_fp8_rows_k<TT, HDD>), grid, block, 0, s, (const TT*)qkv, cu,       \
+                         (uint8_t*)k8, ks, (uint8_t*)v8, vs, N, B, H, G, Tmax, rows, CB);                          \
+    else                                                                                                           \
+      hipLaunchKernelGGL((kv_cache_fill_varlen_fp8_k<TT, HDD>), grid, block, 0, s, (const TT*)qkv, cu,            \
+                         (uint8_t*)k8, ks, (uint8_t*)v8, vs, N, B, H, G, Tmax);                                    \
+  } while (0)
   if (dt == DType::BF16) {
     if (hd == 128) L_(bf16_t, 128); else L_(bf16_t, 64);
   } else {

@@ -692,8 +692,26 @@ Tensor attn_decode_append_rows(const Tensor& qkv, Tensor& kc, Tensor& vc, const 
 
 // qkv [N, (H+2G)*hd] packed rows, sequence b = rows [cu[b], cu[b+1]) (cu int32 [B+1], lengths
 // <= Tmax: the caller's host bounds); kc / vc [B, G, Tmax, hd]: rows t < len_b of (b, g) <- the k / v
-// of qkv row cu[b] + t, nothing else written
-void kv_cache_fill_varlen(const Tensor& qkv, const Tensor& cu, Tensor& kc, Tensor& vc) {
+// of qkv row cu[b] + t, nothing else written.  rows (int32 [n], n <= B): the batch has n sequences
+// (cu int32 [n+1]) and sequence i goes to cache row rows[i]; the host wrapper has checked the values
+// distinct and inside [0, B), the kernel skips a row outside that range
+int fill_rows(const Op& op, const optional<Tensor>& rows_, const Tensor& cu, int64_t B, const int** rows) {
+  *rows = nullptr;
+  if (const Tensor* r = opt(rows_)) {
+    op.contig(*r, "rows");
+    op.dtype(*r, at::kInt, "rows");
+    TORCH_CHECK(r->dim() == 1 && r->numel() <= B, op.name, ": rows must be 1-D with at most the cache's ", B,
+                " rows, got ", r->sizes());
+    op.vec(cu, r->numel() + 1, at::kInt, "cu");
+    *rows = r->data_ptr<int>();
+    return op.to_int(r->numel(), "sequences");
+  }
+  op.vec(cu, B + 1, at::kInt, "cu");
+  return op.to_int(B, "B");
+}
+
+void kv_cache_fill_varlen(const Tensor& qkv, const Tensor& cu, Tensor& kc, Tensor& vc,
+                          const optional<Tensor>& rows_) {
   Op op("kv_cache_fill_varlen", qkv, "qkv");
   op.dense(qkv, "qkv");
   op.dims(qkv, 2, "qkv");
@@ -707,10 +725,11 @@ void kv_cache_fill_varlen(const Tensor& qkv, const Tensor& cu, Tensor& kc, Tenso
               "kv_cache_fill_varlen: cache ", kc.sizes(), " must be non-empty with 16-byte aligned head rows");
   TORCH_CHECK(qkv.size(1) % hd == 0 && qkv.size(1) / hd > 2 * G, "kv_cache_fill_varlen: qkv ", qkv.sizes(),
               " is not [N, (H + 2G) hd] for the cache's G ", G, " and hd ", hd);
-  op.vec(cu, B + 1, at::kInt, "cu");
-  bllm::kv_cache_fill_varlen(qkv.data_ptr(), cu.data_ptr<int>(), kc.data_ptr(), vc.data_ptr(), N, op.to_int(B, "B"),
+  const int* rows;
+  const int nseq = fill_rows(op, rows_, cu, B, &rows);
+  bllm::kv_cache_fill_varlen(qkv.data_ptr(), cu.data_ptr<int>(), kc.data_ptr(), vc.data_ptr(), N, nseq,
                              op.to_int(qkv.size(1) / hd - 2 * G, "H"), op.to_int(G, "G"), op.to_int(Tmax, "Tmax"),
-                             op.to_int(row_bytes, "row bytes"), stream());
+                             op.to_int(row_bytes, "row bytes"), stream(), rows, op.to_int(B, "B"));
 }
 
 // q [B, H, hd]; kc / vc [B, G, Tmax, hd] with the first L positions valid -> out [B, H*hd]
@@ -805,17 +824,19 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> fp8_caches(const Op& op, const Te
 }
 
 // kv_cache_fill_varlen into an fp8 cache: rows t < len_b of (b, g) <- the quantised k / v of qkv
-// row cu[b] + t and their scales, nothing else written
-void kv_cache_fill_varlen_fp8(const Tensor& qkv, const Tensor& cu, Tensor& k8, Tensor& ks, Tensor& v8, Tensor& vs) {
+// row cu[b] + t and their scales, nothing else written; rows as in kv_cache_fill_varlen
+void kv_cache_fill_varlen_fp8(const Tensor& qkv, const Tensor& cu, Tensor& k8, Tensor& ks, Tensor& v8, Tensor& vs,
+                              const optional<Tensor>& rows_) {
   Op op("kv_cache_fill_varlen_fp8", qkv, "qkv");
   const auto [B, G, Tmax, hd] = fp8_caches(op, qkv, k8, ks, v8, vs);
   TORCH_CHECK(qkv.size(1) % hd == 0 && qkv.size(1) / hd > 2 * G, "kv_cache_fill_varlen_fp8: qkv ", qkv.sizes(),
               " is not [N, (H + 2G) hd] for the cache's G ", G, " and hd ", hd);
-  op.vec(cu, B + 1, at::kInt, "cu");
+  const int* rows;
+  const int nseq = fill_rows(op, rows_, cu, B, &rows);
   bllm::kv_cache_fill_varlen_fp8(dt_of(qkv), qkv.data_ptr(), cu.data_ptr<int>(), k8.data_ptr(), ks.data_ptr<float>(),
-                                 v8.data_ptr(), vs.data_ptr<float>(), qkv.size(0), op.to_int(B, "B"),
+                                 v8.data_ptr(), vs.data_ptr<float>(), qkv.size(0), nseq,
                                  op.to_int(qkv.size(1) / hd - 2 * G, "H"), op.to_int(G, "G"), (int)hd, (int)Tmax,
-                                 stream());
+                                 stream(), rows, op.to_int(B, "B"));
 }
 
 // attn_decode_append_rows on an fp8 cache: row b's new k / v are quantised into cache row pos[b]
@@ -1636,8 +1657,8 @@ TORCH_LIBRARY(bllm, m) {
   BLLM_OP("attn_decode_append_split(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, int H, int G) -> Tensor", attn_decode_append_split);
   BLLM_OP("attn_extend_rows(Tensor qkv, Tensor(a!) kcache, Tensor(b!) vcache, Tensor pos, Tensor pos_rows, int Q, int H, int G) -> Tensor", attn_extend_rows);
   BLLM_OP("spec_advance_(Tensor(a!) idx, Tensor samp, Tensor(b!) hist, Tensor h0, Tensor(c!) pos, Tensor(d!) ctr, Tensor(e!) nsteps, Tensor(f!) finished, Tensor(g!) out, int eos_id, int ngram, bool accept) -> ()", spec_advance_);
-  BLLM_OP("kv_cache_fill_varlen(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) vcache) -> ()", kv_cache_fill_varlen);
-  BLLM_OP("kv_cache_fill_varlen_fp8(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale) -> ()", kv_cache_fill_varlen_fp8);
+  BLLM_OP("kv_cache_fill_varlen(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) vcache, Tensor? rows=None) -> ()", kv_cache_fill_varlen);
+  BLLM_OP("kv_cache_fill_varlen_fp8(Tensor qkv, Tensor cu, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale, Tensor? rows=None) -> ()", kv_cache_fill_varlen_fp8);
   BLLM_OP("attn_decode_append_rows_fp8(Tensor qkv, Tensor(a!) kcache, Tensor(b!) kscale, Tensor(c!) vcache, Tensor(d!) vscale, Tensor pos, int H, int G) -> Tensor", attn_decode_append_rows_fp8);
   BLLM_OP("rope_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, int H, int G, int hd, Tensor pos) -> ()", rope_dev_);
   BLLM_OP("rope_pos_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos_ids, int H, int G, int hd, bool inverse) -> ()", rope_pos_);

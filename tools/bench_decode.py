@@ -49,7 +49,20 @@ unhinted arm of the same K gave (``--hints plain``: the plain loop's; in bf16 a 
 near-tied logits round differently in a 1-token and a (K + 1)-token step, the two answers part after
 some tokens and the hint stops matching there).  Per arm: ms per generated token, verify steps
 per row, accepted drafts per step and whether the tokens equal the plain loop's.
-Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128 --speculative 3,7 --hints self"""
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --ragged 1,8,32 --tokens 128 --speculative 3,7 --hints self
+
+``--continuous S1,S2,... [--budgets LO,HI] [--weight_dtype fp8]``: continuous batching
+(``generate_continuous``) against static batches over the first 4 S synthetic Alpaca prompts.
+Random-init weights never emit eos on cue, so every prompt gets a seeded budget, uniform in LO..HI
+(default 16,128; LO = HI: equal budgets, where continuous batching can only lose): BUDGETS STAND IN
+FOR ANSWER LENGTHS.  ``static``: ``generate_ragged`` over consecutive groups of S prompts, each
+group run with its largest budget and its answers cut to their own budgets -- a static batch that
+stops when its longest row is done.  ``continuous``: one ``generate_continuous`` call with S slots
+and the per-prompt budgets.  Both greedy through the device sampler, interleaved A B A B in one
+process, ``--repeats`` times after one warm-up of each; ms per KEPT token (sum of the budgets),
+median and range, and next to it the schedule's own arithmetic: the static arm's decode steps,
+sum over groups of (largest budget - 1), against the continuous arm's ``replays`` and ``prefills``.
+Usage: python tools/bench_decode.py --model llama3_2 --num_params 1B --continuous 8,32 --budgets 16,128"""
 import argparse
 import json
 import os
@@ -266,6 +279,66 @@ def ragged_speculative(a, m, cfg):
             json.dump(rows, f, indent=1)
 
 
+def continuous(a, m, cfg):
+    sizes = [int(b) for b in a.continuous.split(",")]
+    lo, hi = (int(v) for v in a.budgets.split(","))
+    prompts, tok_name = _alpaca_prompts(a.model, cfg, 4 * max(sizes))
+    ctx = cfg.context_length
+    kv = None if a.kv_dtype == "model" else a.kv_dtype
+    packs = m.new_decode_weights(a.weight_dtype) if a.weight_dtype != "model" else None
+    rows = []
+    for S in sizes:
+        ps = prompts[:4 * S]
+        g = torch.Generator().manual_seed(a.seed)
+        budgets = torch.randint(lo, hi + 1, (len(ps),), generator=g).tolist()
+        groups = [range(i, min(i + S, len(ps))) for i in range(0, len(ps), S)]
+        stats = {}
+
+        def run_static():
+            res = []
+            for grp in groups:
+                out = G.generate_ragged(m, [ps[i] for i in grp], max(budgets[i] for i in grp), ctx, seed=0,
+                                        kv_dtype=kv, weight_dtype=packs)
+                res += [r[:ps[i].numel() + budgets[i]] for i, r in zip(grp, out)]
+            return res
+
+        def run_continuous():
+            return G.generate_continuous(m, ps, budgets, ctx, S, seed=0, kv_dtype=kv, weight_dtype=packs, stats=stats)
+
+        a_out, b_out = run_static(), run_continuous()         # also the warm-up of each
+        same = sum(bool(torch.equal(x, y)) for x, y in zip(a_out, b_out))
+        ta, tb = [], []
+        for _ in range(a.repeats):
+            ta.append(_timed(run_static))
+            tb.append(_timed(run_continuous))
+        kept = sum(budgets)
+
+        def arm(times):
+            ms = sorted(1000 * t / kept for t in times)
+            return {"ms_per_kept_token": round(statistics.median(ms), 4),
+                    "ms_per_kept_token_range": [round(ms[0], 4), round(ms[-1], 4)]}
+
+        lens = [int(p.numel()) for p in ps]
+        static_steps = sum(max(budgets[i] for i in grp) - 1 for grp in groups)
+        row = {"model": f"{a.model}-{a.num_params}", "slots": S, "prompts": len(ps), "repeats": a.repeats,
+               "note": "budgets stand in for answer lengths (random-init weights emit no eos on cue)",
+               "budgets": {"lo": lo, "hi": hi, "seed": a.seed, "sum": kept, "mean": round(kept / len(ps), 1)},
+               "tokenizer": tok_name, "prompt_tokens": {"min": min(lens), "max": max(lens), "sum": sum(lens)},
+               "kv_dtype": a.kv_dtype, "weight_dtype": a.weight_dtype,
+               "graph": os.environ.get("BLLM_DECODE_GRAPH", "default"),
+               "static": dict(arm(ta), decode_steps=static_steps, prefills=len(groups)),
+               "continuous": dict(arm(tb), decode_steps=stats["replays"], prefills=stats["prefills"]),
+               "answers_equal": f"{same}/{len(ps)}"}
+        row["step_ratio"] = round(static_steps / max(stats["replays"], 1), 3)
+        row["time_ratio"] = round(row["static"]["ms_per_kept_token"] / row["continuous"]["ms_per_kept_token"], 3)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def context_bench(a, m, cfg):
     ctx = cfg.context_length
     if a.prompt + a.tokens > ctx:
@@ -379,6 +452,10 @@ def main():
     ap.add_argument("--hints", default="none", choices=["none", "self", "plain"],
                     help="--speculative: adds arms hinted with each prompt and its own answer (self: the unhinted "
                          "speculative arm's, plain: the plain loop's)")
+    ap.add_argument("--continuous", default=None,
+                    help="comma list of slot counts S: generate_continuous against static batches of S over 4 S "
+                         "prompts with seeded budgets (see above)")
+    ap.add_argument("--budgets", default="16,128", help="--continuous: per-prompt budgets uniform in LO,HI (--seed)")
     a = ap.parse_args()
     ops.load_ext(required=True)
     cfg = (get_config(a.model, a.num_params) if a.context is None
@@ -397,6 +474,8 @@ def main():
     m.flatten()
     if a.graph is not None:
         os.environ["BLLM_DECODE_GRAPH"] = str(a.graph)
+    if a.continuous:
+        return continuous(a, m, cfg)
     if a.ragged and a.speculative:
         return ragged_speculative(a, m, cfg)
     if a.ragged and a.weight_dtype in ("fp8", "mxfp4"):

@@ -77,6 +77,7 @@ def _normalise(path: str, rename: bool) -> list[str]:
 
 # per-file numbering of local labels, in label definitions, operands and loop comments
 _LOCAL = re.compile(r"(\.L|\b)(BB|func_end|func_begin|JTI|tmp)\d+")
+_PAD = re.compile(r"[ \t]+;")
 
 
 def _kernels(lines: list[str]) -> dict[str, list[str]]:
@@ -115,8 +116,10 @@ def _kernels(lines: list[str]) -> dict[str, list[str]]:
             cur = out.setdefault(m.group(1), [])
         elif ln.startswith("\t.section\t.AMDGPU.gpr_maximums"):
             cur = None
-        if cur is not None and not ln.startswith("\t.section\t.text."):
-            cur.append(_LOCAL.sub(lambda k: k.group(1) + k.group(2), ln))
+        # "\t.text" opens the NEXT function (absent after a file's last one), and a label's comment
+        # column moves with the width of the label number that was dropped: neither is kernel text
+        if cur is not None and not ln.startswith("\t.section\t.text.") and ln != "\t.text":
+            cur.append(_PAD.sub(" ;", _LOCAL.sub(lambda k: k.group(1) + k.group(2), ln)))
     return out
 
 
